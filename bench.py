@@ -4,8 +4,14 @@
 Workload (default, configs[1]): DeepFM fp32, 39 fields / 1M vocab / k = 16, fcDims 400,400,400,
 over a 1M-row synthetic set whose ids and table live in HBM before timing starts.  One step =
 one forward (gather + first order + FM + tower + sigmoid) over one batch of --batch rows of that
-set; successive steps walk the set.  The default line also carries an "models.xdeepfm" sub-record
-(configs[2], CIN 200,200,200 at B = 16,384): BASELINE.json's metric names DeepFM and xDeepFM.
+set; successive steps walk the set.  A plain run does only that: set up, settle the clock, W warm-up
+steps, the K timed steps, the line (value, ms_per_step).  `--dump-outputs DIR` adds the last timed
+step's outputs as DIR/<name>.npy (same arguments, same inputs: two builds compare output for output).
+`--full` adds everything else: per-stage times and the dominant kernel's roofline, the predict loop +
+AUC, the parity check against the oracle, the CPU baseline, and for deepfm the "models.xdeepfm"
+sub-record (configs[2], CIN 200,200,200 at B = 16,384: BASELINE.json's metric names DeepFM and
+xDeepFM), the encoder and L-A sub-records and, at N > 1, the sharded one.  The --no-* options below
+trim a --full run.
 Other workloads: xdeepfm, deepfm_sharded (configs[3]), dcn_bf16 / pnn_bf16 (configs[4]),
 lr_plumbing (configs[0]: LIBSVM text -> parse -> LR predict -> AUC), deepfm_train / xdeepfm_train.
 
@@ -15,8 +21,8 @@ no GPU call and imports nothing of librmx), or runs as one rank of an external
 `torch.distributed.run` (WORLD_SIZE set).  Every rank owns a replica of the 1M-row table and its own
 batches (replicas only: the V = 1M forward has no exchange step), so scaling is weak and value = sum
 of all ranks' examples / max rank time; deepfm_sharded hash-shards the 100M-row table over the ranks
-(RCCL exchange per batch).  At N > 1 every rank checks its own bench rows against the oracle after
-timing (`parity_check_ranks`).
+(RCCL exchange per batch).  At N > 1 with --full every rank checks its own bench rows against the oracle
+after timing (`parity_check_ranks`).
 
 Prints ONE JSON line (rank 0).  Only the cpu_baseline leg touches oracle/ (the checker).
 """
@@ -63,6 +69,14 @@ def parse():
     ap.add_argument("--workload", choices=["deepfm", "xdeepfm", "xdeepfm_cin1", "deepfm_sharded", "dcn_bf16",
                                            "pnn_bf16", "deepfm_train", "xdeepfm_train", "lr_plumbing", "encoder"],
                     default="deepfm")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the per-stage times and the roofline of the "
+                         "dominant kernel, the predict loop + AUC, the parity check against the oracle, the CPU "
+                         "baseline and (deepfm) the xDeepFM, sharded, encoder and L-A sub-records.  Without it a run "
+                         "sets up, settles, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed (the arrays its caller "
+                         "receives) as DIR/<name>.npy in float32: at most 64 MB, a seeded sample of a larger array")
     ap.add_argument("--no-encoder-record", action="store_true",
                     help="deepfm: skip the encoder sub-record (gather + first order + FM alone at V = 1M and 100M)")
     ap.add_argument("--enc-table", choices=["row", "line", "both"], default="both",
@@ -95,9 +109,37 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="bounded CPU-baseline budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--parity-only", action="store_true",
-                    help="no CPU timing, but the parity check of the predicted rows against the fp64 oracle (grids)")
+                    help="with --full: no CPU timing, but the parity check of the predicted rows against the fp64 "
+                         "oracle (grids)")
     ap.add_argument("--set", default="", help="kernel knobs before building the model, k=v,k=v (rmx_set_tuning)")
     return ap.parse_args()
+
+
+DUMP_ARRAY_BYTES = 16 << 20  # --dump-outputs: a larger array is sampled down to this
+DUMP_TOTAL_BYTES = 64 << 20
+SEED_DUMP = 0xD0_0D
+
+
+def dump_sample(a):
+    """float32 copy of an output array for --dump-outputs; an array over DUMP_ARRAY_BYTES is cut to a fixed
+    sample of its elements (sorted flat indices drawn from SEED_DUMP and the array's size, so two builds
+    sample the same elements)."""
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    m = DUMP_ARRAY_BYTES // 4
+    if a.size <= m:
+        return a
+    idx = np.sort(np.random.default_rng([SEED_DUMP, a.size]).integers(0, a.size, m))
+    return a[idx]
+
+
+def write_dump(path, arrays, rank=0):
+    """--dump-outputs: DIR/<name>.npy per array (rank r > 0: <name>_rank<r>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_TOTAL_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs exceed the %d-byte cap" % (total, DUMP_TOTAL_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
 
 
 def stage_work(workload, stage, B, direct=False):
@@ -457,6 +499,10 @@ def run_plumbing(args, rmx, ctx, rank, world, dist, steps, warmup):
     if dist:
         dist.barrier()
     t_rank = max_over_ranks(dist, t_rank)
+    dump = {"scores": dump_sample(scores.numpy()), "auc": dump_sample([res["auc"]])} if args.dump_outputs else None
+    if not args.full:
+        return {"value": world * PLUMB_ROWS * steps / t_rank, "ms_per_step": t_rank * 1e3 / steps, "B": PLUMB_ROWS,
+                "Vw": V, "nrows": PLUMB_ROWS, "auc": res.get("auc"), "dump": dump}
     model.set_timing(True)
     step()
     stages, calls = model.get_timing()
@@ -472,7 +518,7 @@ def run_plumbing(args, rmx, ctx, rank, world, dist, steps, warmup):
             "note": "100-row launches: latency-bound plumbing (the parse on the host dominates the pass)"}
     return {"value": world * B * steps / t_rank, "ms_per_step": t_rank * 1e3 / steps, "B": B, "Vw": V,
             "nrows": PLUMB_ROWS, "roofline": roof, "stages": per_stage, "auc": res.get("auc"),
-            "out": scores.numpy()}
+            "out": scores.numpy(), "dump": dump}
 
 
 def max_over_ranks(dist, t):
@@ -487,7 +533,7 @@ def max_over_ranks(dist, t):
 ENC_VOCABS = (1_000_000, 100_000_000)
 
 
-def run_encoder(args, rmx, ctx, steps, warmup, Vw, B=65536):
+def run_encoder(args, rmx, ctx, steps, warmup, Vw, B=65536, dump=None):
     """The encoder alone (rmx_encoder_ids: gather + first order + FM of DeepFM, encoder_k16v2_kernel) at
     vocabulary Vw, with the [V][k] row table + [V] weights and with the [V][32] line copy (one 128-B line per
     id: knob table_lines), timed with HIP events on its stream: examples/s, algorithmic GB/s (2,812 B per
@@ -536,6 +582,8 @@ def run_encoder(args, rmx, ctx, steps, warmup, Vw, B=65536):
             ms = ctypes.c_float()
             lib.rmx_event_elapsed_ms(ev0, ev1, ctypes.byref(ms))
             avg_s = ms.value / 1e3 / steps
+            if dump is not None:  # y of the last timed launch (of the layout timed last)
+                dump["y"] = dump_sample(y.view(((steps - 1) % nb) * B, B).numpy())
             lines_per_ex = F if lines else 2 * F  # + the ids' own lines (156 B per example, streamed)
             ent = {"avg_ms": round(avg_s * 1e3, 4), "examples_per_s": round(B / avg_s, 1),
                    "achieved_gbs": round(B * bpe / avg_s / 1e9, 1),
@@ -792,6 +840,11 @@ def run(args, workload, rmx, ctx, rank, world, dist, steps, warmup, B=0):
                 step(settle)
                 settle += 1
             ctx.sync()
+    if overlap and args.dump_outputs:
+        # the settle loop runs as many steps as its time allows, and the overlapped pipeline counts its own
+        # batches: restart it at batch 0, so the batch of the last timed step is the same from run to run
+        drain()
+        pipe["j"] = 0
     for i in range(warmup):
         step(i)
     ctx.sync()
@@ -818,7 +871,20 @@ def run(args, workload, rmx, ctx, rank, world, dist, steps, warmup, B=0):
     t_rank = max_over_ranks(dist, max(wall, ms.value / 1e3))
     value = world * B * steps / t_rank
 
+    dump = None
+    if args.dump_outputs:  # what the last timed step handed back, read before anything else runs
+        if train:
+            dump = {n: dump_sample(a.numpy()) for n, a in (("grad_bias", g_b), ("grad_weights", g_w),
+                                                           ("grad_embedding", g_e), ("grad_mats", g_m),
+                                                           ("loss", g_loss))}
+        else:
+            last = (pipe["j"] - 1) if overlap else (warmup + steps - 1)
+            dump = {"out": dump_sample(views[last % nb][1].numpy())}
     drain()  # (overlap) the pull of the batch after the last timed one
+    split = not bf16 and rmx.get_tuning("f32_split", 1) != 0
+    if not args.full:
+        return {"value": value, "ms_per_step": t_rank * 1e3 / steps, "B": B, "Vw": Vw, "nrows": nrows,
+                "settle_steps": settle, "bf16": bf16, "split": split, "dump": dump}
     # ---- roofline of the dominant kernel: per-stage HIP events on the launch stream ----
     # (deepfm_sharded: measured on the one-stream path, exchange and forward in sequence)
     model.set_timing(True)
@@ -832,7 +898,6 @@ def run(args, workload, rmx, ctx, rank, world, dist, steps, warmup, B=0):
     model.set_timing(False)
     if sharded and not args.no_overlap:
         overlap = saved
-    split = not bf16 and rmx.get_tuning("f32_split", 1) != 0
 
     def peak_of(stage):
         if bf16:
@@ -913,7 +978,7 @@ def run(args, workload, rmx, ctx, rank, world, dist, steps, warmup, B=0):
     res = {"value": value, "ms_per_step": t_rank * 1e3 / steps, "B": B, "Vw": Vw, "nrows": nrows,
            "roofline": roof, "stages": per_stage, "stage_sum_ms": round(stage_sum, 4), "predict_auc": pa,
            "settle_steps": settle,
-           "out": out.numpy()[:512], "bf16": bf16, "split": split,
+           "out": out.numpy()[:512], "bf16": bf16, "split": split, "dump": dump,
            "ids_head": ids.numpy()[:512 * F] if args.zipf else None}
     if sharded:
         res["exchange"] = {"dedupe": "off" if args.no_dedupe else ("on" if args.dedupe_on else "auto"),
@@ -1072,7 +1137,10 @@ def main():
     if args.workload == "encoder":
         # the encoder alone (profiling / its own line): V = --vocab (default 100M), B = --batch (65,536)
         Vw = args.vocab or 100_000_000
-        rec = run_encoder(args, rmx, ctx, args.steps, args.warmup, Vw, B=args.batch or 65536)
+        dump = {} if args.dump_outputs else None
+        rec = run_encoder(args, rmx, ctx, args.steps, args.warmup, Vw, B=args.batch or 65536, dump=dump)
+        if dump:
+            write_dump(args.dump_outputs, dump, rank)
         if rank == 0:
             lay = "row_table" if "row_table" in rec else "line_table"
             ent = rec[lay]
@@ -1091,12 +1159,20 @@ def main():
     r = run(args, args.workload, rmx, ctx, rank, world, dist, args.steps, args.warmup)
     # BASELINE.json's metric names DeepFM AND xDeepFM: the default line measures both (xDeepFM as a
     # sub-record with its own steps, roofline, parity and CPU baseline; configs[2])
+    # (only with --full: a plain run ends with the headline figure)
     companion = None
-    if args.workload == "deepfm" and not args.no_companion:
+    if args.full and args.workload == "deepfm" and not args.no_companion:
         companion = run(args, "xdeepfm", rmx, ctx, rank, world, dist, args.steps, args.warmup, B=16384)
+    if args.dump_outputs:
+        dump = dict(r["dump"])
+        if companion:
+            dump.update(("xdeepfm_" + n, a) for n, a in companion["dump"].items())
+        write_dump(args.dump_outputs, dump, rank)
     cpu = cpu2 = None
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not train and not args.parity_only
-    if rank == 0 and world == 1 and args.parity_only and not train and args.workload != "lr_plumbing":
+    want_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not train
+                and not args.parity_only)
+    if (args.full and rank == 0 and world == 1 and args.parity_only and not train
+            and args.workload != "lr_plumbing"):
         cpu = {"parity_check": parity_check(args.workload, r["out"], 0, vocab=r["Vw"], ids_host=r.get("ids_head"))}
         if companion:
             cpu2 = {"parity_check": parity_check("xdeepfm", companion["out"], 0)}
@@ -1116,7 +1192,7 @@ def main():
     # N > 1: every rank checks rows of its own bench set against the oracle (after timing), rank 0
     # reports them all
     parity_ranks = None
-    if world > 1 and not train and args.workload != "lr_plumbing" and not args.zipf:
+    if args.full and world > 1 and not train and args.workload != "lr_plumbing" and not args.zipf:
         pc = parity_check(args.workload, r["out"], rank * r["nrows"], vocab=r["Vw"])
         if companion:
             pc = {"deepfm": pc, "xdeepfm": parity_check("xdeepfm", companion["out"], rank * companion["nrows"])}
@@ -1152,15 +1228,16 @@ def main():
                                 "(rmx_table::line, knob table_lines)"}
                if args.workload == "deepfm" and rmx.get_tuning("table_lines", 0) else {}),
             **({"exchange": r["exchange"]} if "exchange" in r else {}),
-            "roofline": r["roofline"],
-            "cpu_baseline": cpu,
+            **({"roofline": r["roofline"], "cpu_baseline": cpu} if args.full else {}),
             **({"parity_check_ranks": parity_ranks,
                 "parity_ok": all(_pc_ok(p) for p in parity_ranks)}
                if parity_ranks else {}),
             **({"predict_auc": r["predict_auc"]} if r.get("predict_auc") else {}),
             **({"auc": r["auc"]} if "auc" in r else {}),
-            "stages": r["stages"],
+            **({"stages": r["stages"]} if args.full else {}),
             **({"stage_sum_ms": r["stage_sum_ms"]} if "stage_sum_ms" in r else {}),
+            **({"outputs": {"dir": args.dump_outputs, "arrays": {n: int(a.size) for n, a in r["dump"].items()}}}
+               if args.dump_outputs else {}),
         }
         if companion:
             line["models"] = {"xdeepfm": {
@@ -1184,8 +1261,8 @@ def main():
     # and check the exchange.  A watchdog bounds it: past --companion-timeout it aborts the RCCL
     # communicator, prints the line with the sub-record marked as timed out and ends the process.
     sub = None
-    if (args.workload == "deepfm" and not args.no_companion and not args.no_sharded_companion and not args.zipf
-            and ((world > 1 and world <= ndev) or args.sharded_companion)):
+    if (args.full and args.workload == "deepfm" and not args.no_companion and not args.no_sharded_companion
+            and not args.zipf and ((world > 1 and world <= ndev) or args.sharded_companion)):
         sub = sharded_companion(args, rmx, ctx, rank, world, dist, line if rank == 0 else None)
         if rank == 0:
             line.setdefault("models", {})["deepfm_sharded"] = sub
@@ -1193,7 +1270,7 @@ def main():
     # N > 1): the encoder alone (gather + first order + FM) at V = 1M and 100M, its HBM
     # roofline, and the L-A drop-in (host arrays) at the reference's batch sizes
     enc = la = None
-    if args.workload == "deepfm" and not args.zipf and rank == 0:
+    if args.full and args.workload == "deepfm" and not args.zipf and rank == 0:
         if not args.no_encoder_record:
             enc = encoder_record(args, rmx, ctx, max(20, min(args.steps, 100)), max(5, args.warmup))
             line.setdefault("models", {})["encoder"] = enc

@@ -7,7 +7,7 @@ tail -2 $O/pytest.log
 for w in dcn_bf16 pnn_bf16; do
   for v in ${VARS:-default 6 default 6}; do
     if [ $v = default ]; then SET=""; else SET="--set tower_variant=$v"; fi
-    timeout -k 10 120 python bench.py --workload $w --steps 100 --warmup 10 --no-cpu-baseline $SET > $O/${w}_$v.json || exit 1
+    timeout -k 10 120 python bench.py --full --workload $w --steps 100 --warmup 10 --no-cpu-baseline $SET > $O/${w}_$v.json || exit 1
     python3 -c "
 import json; d=json.load(open('$O/${w}_$v.json')); print('$w var=$v', round(d['value']/1e6,1), d['ms_per_step'], {k: v['avg_ms'] for k, v in d['stages'].items()})"
   done

@@ -9,7 +9,7 @@ i=0
 for kv in "$@"; do
   args=""
   [ "$kv" != "-" ] && args="--set $kv"
-  timeout -k 10 300 python bench.py --workload $WL --no-cpu-baseline --no-companion $args > $O/ab_$i.json 2> $O/ab_$i.err || { tail -5 $O/ab_$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $WL --no-cpu-baseline --no-companion $args > $O/ab_$i.json 2> $O/ab_$i.err || { tail -5 $O/ab_$i.err; exit 1; }
   python3 -c "
 import json,sys; d=json.load(open('$O/ab_$i.json'))
 print('%-28s %12.0f %8.4f ms' % ('$kv', d['value'], d['ms_per_step']), {k: v['avg_ms'] for k, v in d['stages'].items()})"

@@ -11,11 +11,11 @@ for rep in 1 2; do
     [ "$lib" = default ] && tag=default
     case $lib in set:*) tag=${lib#set:}; tag=${tag//,/_};; esac
     if [ "$lib" = default ]; then
-      timeout -k 10 200 python bench.py --no-cpu-baseline --no-companion $ARGS > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-companion $ARGS > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
     elif [ "${lib#set:}" != "$lib" ]; then  # set:k=v,k=v -- knobs on the in-tree library
-      timeout -k 10 200 python bench.py --no-cpu-baseline --no-companion --set "${lib#set:}" $ARGS > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-companion --set "${lib#set:}" $ARGS > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
     else
-      RMX_LIB=$lib timeout -k 10 200 python bench.py --no-cpu-baseline --no-companion $ARGS > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
+      RMX_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-companion $ARGS > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
     fi
     rc=$?
     if [ $rc -ne 0 ]; then echo "$tag rep $rep rc=$rc"; tail -3 "$OUT/$tag.$rep.err"; exit $rc; fi

@@ -20,17 +20,17 @@ case $PHASE in
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
     ;;
   driver)
-    step bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5
+    step bench_driver 600 python bench.py --full --gpus 1 --steps 20 --warmup 5
     step prof_driver 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_driver" -o deepfm -- \
-      python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-companion
+      python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-companion
     ;;
   lines)
     for wl in xdeepfm dcn_bf16 pnn_bf16; do
-      step bench_$wl 600 python bench.py --workload $wl --no-companion
+      step bench_$wl 600 python bench.py --full --workload $wl --no-companion
       step prof_$wl 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$wl" -o $wl -- \
-        python3 bench.py --workload $wl --no-cpu-baseline --no-companion --steps 20 --warmup 5
+        python3 bench.py --full --workload $wl --no-cpu-baseline --no-companion --steps 20 --warmup 5
     done
-    step bench_deepfm_sharded 600 python bench.py --workload deepfm_sharded --no-companion
+    step bench_deepfm_sharded 600 python bench.py --full --workload deepfm_sharded --no-companion
     ;;
   grid)
     step grid 1100 bash tools/grid_r04.sh "$O/grid"

@@ -9,7 +9,7 @@ PARTS=${*:-"deepfm xdeepfm zipf"}
 mkdir -p "$O"
 line() {  # line <tag> <bench args...>
   local tag=$1; shift
-  timeout -k 10 200 python bench.py --no-companion --parity-only "$@" > "$O/$tag.json" 2> "$O/$tag.err"
+  timeout -k 10 200 python bench.py --full --no-companion --parity-only "$@" > "$O/$tag.json" 2> "$O/$tag.err"
   local rc=$?
   if [ $rc -ne 0 ]; then echo "$tag rc=$rc"; tail -3 "$O/$tag.err"; exit $rc; fi
   python3 - "$O/$tag.json" "$tag" <<'EOF' | tee -a "$O/summary.txt"

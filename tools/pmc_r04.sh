@@ -18,7 +18,7 @@ for wl in $WLS; do
     mkdir -p "$O/pmc_$wl"
     echo "== pmc_${wl}_$pass: $ctr" | tee -a "$O/steps.log"
     timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d "$O/pmc_$wl/$pass" -o "$pass" -- \
-      python3 bench.py --workload "$wl" --steps $steps --warmup 2 --no-cpu-baseline --no-companion --settle-ms 0 \
+      python3 bench.py --full --workload "$wl" --steps $steps --warmup 2 --no-cpu-baseline --no-companion --settle-ms 0 \
       > "$O/pmc_$wl/$pass.log" 2>&1
     rc=$?
     echo "== pmc_${wl}_$pass rc=$rc" | tee -a "$O/steps.log"

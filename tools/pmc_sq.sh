@@ -11,7 +11,7 @@ for ctr in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
            "GRBM_GUI_ACTIVE GRBM_COUNT" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i + 1))
   timeout -s KILL 120 rocprofv3 --pmc $ctr --output-format csv -d "$O/$TAG/p$i" -o p$i -- \
-    python3 bench.py $ARGS --steps 5 --warmup 2 --no-cpu-baseline --no-companion --settle-ms 0 > "$O/$TAG/p$i.log" 2>&1
+    python3 bench.py --full $ARGS --steps 5 --warmup 2 --no-cpu-baseline --no-companion --settle-ms 0 > "$O/$TAG/p$i.log" 2>&1
   rc=$?
   echo "$TAG pass $i ($ctr) rc=$rc"
   [ $rc -ne 0 ] && exit $rc

@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/procs}
 mkdir -p "$OUT"
 ps -o pid,ppid,pgid,sid,stat,etime,cmd -s $$ > "$OUT/before.txt" 2>&1
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench rc=$?" > "$OUT/rc.txt"
 sleep 2
 ps -o pid,ppid,pgid,sid,stat,etime,cmd -s $$ > "$OUT/after.txt" 2>&1

@@ -4,7 +4,7 @@ set -u
 TAG=$1; WL=$2; shift 2
 export TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $WL -- python3 bench.py --workload $WL --no-cpu-baseline "$@" > $O/log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $WL -- python3 bench.py --full --workload $WL --no-cpu-baseline "$@" > $O/log 2>&1 || exit 1
 python3 - "$O" <<'PY'
 import csv, glob, sys
 rows = list(csv.DictReader(open(glob.glob(sys.argv[1] + "/*kernel_stats.csv")[0])))
