@@ -218,6 +218,16 @@ int rmx_gen_ids_zipf(rmx_ctx* ctx, uint64_t seed, int64_t row0, int32_t batch, i
  * kernel launched next that reads LDS it never wrote reads that pattern (tests/test_small_s3.py). */
 int rmx_debug_fill_lds(rmx_ctx* ctx, uint32_t pattern, void* stream);
 
+/* Test hook: fill the model's floating-point scratch buffers in HBM -- the inference workspace, the L-A
+ * staging and the backward's state, each over its whole allocated capacity (the largest batch so far, not the
+ * last one) -- with a 32-bit pattern on the stream (NULL: the context's stream), so a kernel of the next call
+ * that reads a pad column or a row past its batch that the call did not write reads the pattern
+ * (tests/test_workspace_leftovers.py).  Buffers of indices, offsets or pointers and state written once
+ * (packed weights, biases, ...) are never touched: the hook cannot turn a leftover into a wild address.
+ * *bytes_filled (nullable): how much was filled.  A model that has never run owns no scratch: RMX_OK, 0 bytes,
+ * no device call.  NULL model: RMX_E_INVALID. */
+int rmx_debug_poison_workspace(rmx_model* model, uint32_t pattern, void* stream, int64_t* bytes_filled);
+
 /* Test hook (host only, no GPU): the slice count S the training dW on the 208 x 208 tile uses for a
  * rows x N x K weight gradient on a device with ncu CUs.  S fixes the dW's fp32 summation order over the
  * slices, so gradients are bitwise reproducible across devices with the same CU count (every 256-CU

@@ -430,6 +430,43 @@ extern "C" int rmx_debug_fill_lds(rmx_ctx* c, uint32_t pattern, void* stream) {
   return RMX_OK;
 }
 
+// Test hook: fills the model's floating-point scratch in HBM with `pattern`, every buffer over its whole
+// allocated capacity (the high-water mark of the batches so far, not the last call's B), so a kernel of the
+// next call that reads a pad column or a row past B that the call did not write sees the pattern rather than
+// whatever the allocator or an earlier, larger batch left there.  The buffers are the ones recorded in
+// rmx_model::scratch where they are allocated: the inference workspace (h, y12, pre2, xcol, xbuf, ubuf, rowdot,
+// opart), the L-A staging (la_E, la_w, la_out, la_E16, la_w16) and the backward's TrainState (x, h, hm, g, fms,
+// p, dz, tmp, xcol, wc, coef, cst, gwc, u, x0, gx0, gu, gpre, dzr, zb, part, part2).
+// Left out on purpose:
+//  - whatever holds indices, offsets or pointers (la_rowptr, the L-A backward's index copy, id buffers): a
+//    leftover read must show up as a wrong number, never as a wild address -- this hook cannot cause a fault;
+//  - state written once and kept: the packed weights and planes, biases, cross_scalars, pairs, the CIN chunk
+//    maps, TrainState's ones / onesR (filled at allocation only);
+//  - the L-A backward's la_grad arrays, which are outputs copied back whole.
+// A model that never ran owns no scratch: RMX_OK, 0 bytes, no HIP call.
+extern "C" int rmx_debug_poison_workspace(rmx_model* m, uint32_t pattern, void* stream, int64_t* bytes_filled) {
+  CHECK_ARG(m, "rmx_debug_poison_workspace: NULL model");
+  if (bytes_filled) *bytes_filled = 0;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->ctx || m->scratch.empty()) return RMX_OK;
+  }
+  RMX_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : m->ctx->stream;
+  ModelUse use(*m, s);  // ordered after the previous call's kernels, before the next call's
+  if (use.st) return use.st;
+  int64_t total = 0;
+  for (const auto& b : m->scratch) {
+    const size_t words = b.bytes / 4;
+    if (words) RMX_HIP(hipMemsetD32Async((hipDeviceptr_t)b.ptr, (int)pattern, words, s));
+    if (b.bytes & 2)  // a bf16 buffer with an odd element count: its last element takes the low half
+      RMX_HIP(hipMemsetD16Async((hipDeviceptr_t)((char*)b.ptr + words * 4), (unsigned short)(pattern & 0xFFFFu), 1, s));
+    total += (int64_t)(b.bytes & ~(size_t)1);
+  }
+  if (bytes_filled) *bytes_filled = total;
+  return RMX_OK;
+}
+
 extern "C" int rmx_gen_ids_zipf(rmx_ctx* c, uint64_t seed, int64_t row0, int32_t B, int32_t F, int64_t V,
                                 double exponent, int32_t* d_ids, void* stream) {
   CHECK_ARG(c && d_ids && B >= 0 && F > 0 && V >= F && exponent > 0.0 && exponent != 1.0,

@@ -144,6 +144,19 @@ void dev_free(T*& p) {
   p = nullptr;
 }
 
+// scratch buffers (workspace, L-A staging): allocated and recorded with their size / forgotten and freed
+int ws_alloc(rmx_model& m, float** p, size_t n) {
+  const int st = dev_alloc(p, n);
+  if (st == RMX_OK) scratch_note(m, *p, sizeof(float) * (n ? n : 1));
+  return st;
+}
+
+template <class T>
+void ws_free(rmx_model& m, T*& p) {
+  scratch_forget(m, p);
+  dev_free(p);
+}
+
 // W^T planes for the backward's dX on the split GEMM (single-block fp32 layers whose input width
 // pads to a multiple of 208 with at most one extra 16-wide tile, e.g. 400 -> 416, 624; the dX buffer's
 // row stride must also hold NTpad, checked at launch: dx_s3_usable)
@@ -169,6 +182,19 @@ int xbuf_ld_max(const rmx_model& m) { return round_up(m.layers[0].Kpad, m.precis
 int xbuf_ld(const rmx_model& m) { return tuning_get("x_line_pad", 1) ? xbuf_ld_max(m) : m.layers[0].Kpad; }
 
 }  // namespace
+
+void scratch_note(rmx_model& m, void* p, size_t bytes) {
+  if (p) m.scratch.push_back({p, bytes});
+}
+
+void scratch_forget(rmx_model& m, void* p) {
+  if (!p) return;
+  for (size_t i = 0; i < m.scratch.size(); ++i)
+    if (m.scratch[i].ptr == p) {
+      m.scratch.erase(m.scratch.begin() + i);
+      return;
+    }
+}
 
 int model_build(rmx_model& m) {
   const int t = m.type;
@@ -456,22 +482,22 @@ void model_release(rmx_model& m) {
   dev_free(m.cross_b);
   dev_free(m.wo_x);
   dev_free(m.pairs);
-  dev_free(m.h[0]);
-  dev_free(m.h[1]);
-  dev_free(m.y12);
-  dev_free(m.pre2);
-  dev_free(m.xcol);
-  dev_free(m.xbuf);
-  dev_free(m.ubuf[0]);
-  dev_free(m.ubuf[1]);
-  dev_free(m.rowdot);
-  dev_free(m.opart);
-  dev_free(m.la_E);
-  dev_free(m.la_w);
-  dev_free(m.la_E16);
-  dev_free(m.la_w16);
+  ws_free(m, m.h[0]);
+  ws_free(m, m.h[1]);
+  ws_free(m, m.y12);
+  ws_free(m, m.pre2);
+  ws_free(m, m.xcol);
+  ws_free(m, m.xbuf);
+  ws_free(m, m.ubuf[0]);
+  ws_free(m, m.ubuf[1]);
+  ws_free(m, m.rowdot);
+  ws_free(m, m.opart);
+  ws_free(m, m.la_E);
+  ws_free(m, m.la_w);
+  ws_free(m, m.la_E16);
+  ws_free(m, m.la_w16);
   dev_free(m.la_rowptr);
-  dev_free(m.la_out);
+  ws_free(m, m.la_out);
   for (auto& p : m.pending) {
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -518,7 +544,8 @@ int model_set_precision(rmx_model& m, int dtype) {
   m.params_ready = false;
   // workspaces depend on Kpad (PNN [x | ip] rows): rebuild on the next call
   RMX_HIP(hipStreamSynchronize(m.ctx->stream));
-  dev_free(m.xbuf);
+  ws_free(m, m.xbuf);
+  m.xbuf_B = 0;
   m.ws_B = 0;
   return RMX_OK;
 }
@@ -581,42 +608,52 @@ int model_load_mats(rmx_model& m, const float* host_mats, bool sync) {
 
 namespace {
 
+// xbuf has a capacity of its own: the paths that need it grow it where they are chosen (PNN and generic k with
+// the workspace, DeepFM's column-split path in model_forward), so which path a call takes never depends on the
+// batch sizes of the model's earlier calls
+int ensure_xbuf(rmx_model& m, int B) {
+  if (B <= m.xbuf_B && m.xbuf) return RMX_OK;
+  RMX_HIP(hipDeviceSynchronize());  // earlier calls on any stream may still read the old buffer
+  ws_free(m, m.xbuf);
+  m.xbuf_B = 0;
+  const int st = ws_alloc(m, &m.xbuf, (size_t)B * xbuf_ld_max(m));
+  if (st == RMX_OK) m.xbuf_B = B;
+  return st;
+}
+
 int ensure_ws(rmx_model& m, int B) {
   if (B <= m.ws_B) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());  // earlier calls on any stream may still read the old buffers
-  dev_free(m.h[0]);
-  dev_free(m.h[1]);
-  dev_free(m.y12);
-  dev_free(m.pre2);
-  dev_free(m.xcol);
-  dev_free(m.xbuf);
-  dev_free(m.ubuf[0]);
-  dev_free(m.ubuf[1]);
-  dev_free(m.rowdot);
-  dev_free(m.opart);
+  ws_free(m, m.h[0]);
+  ws_free(m, m.h[1]);
+  ws_free(m, m.y12);
+  ws_free(m, m.pre2);
+  ws_free(m, m.xcol);
+  ws_free(m, m.ubuf[0]);
+  ws_free(m, m.ubuf[1]);
+  ws_free(m, m.rowdot);
+  ws_free(m, m.opart);
   int st;
   int maxN = 16;
   for (auto& L : m.layers) maxN = std::max(maxN, L.Npad);
   if (!m.layers.empty()) {
-    if ((st = dev_alloc(&m.h[0], (size_t)B * maxN))) return st;
-    if ((st = dev_alloc(&m.h[1], (size_t)B * maxN))) return st;
+    if ((st = ws_alloc(m, &m.h[0], (size_t)B * maxN))) return st;
+    if ((st = ws_alloc(m, &m.h[1], (size_t)B * maxN))) return st;
     // partial logits of an output layer run in column slices (k_gemm_s3.hip)
     // (up to Npad / 16 slices: 208-column slices, or the 32-column blocks of small batches, s3_cols)
-    if ((st = dev_alloc(&m.opart, (size_t)B * (m.layers.back().Npad / 16 + 1)))) return st;
+    if ((st = ws_alloc(m, &m.opart, (size_t)B * (m.layers.back().Npad / 16 + 1)))) return st;
   }
-  if ((st = dev_alloc(&m.y12, B))) return st;
-  if ((st = dev_alloc(&m.pre2, B))) return st;
-  if (m.dcn_fused && (st = dev_alloc(&m.xcol, (size_t)B * (m.cross_depth + 1)))) return st;
-  if (m.type == RMX_MODEL_PNN || (m.type != RMX_MODEL_LR && needs_gather_x(m)) ||
-      (m.type == RMX_MODEL_DEEPFM && B <= tuning_get("s3_cols", kS3ColsMaxB))) {
-    if ((st = dev_alloc(&m.xbuf, (size_t)B * xbuf_ld_max(m)))) return st;
-  }
+  if ((st = ws_alloc(m, &m.y12, B))) return st;
+  if ((st = ws_alloc(m, &m.pre2, B))) return st;
+  if (m.dcn_fused && (st = ws_alloc(m, &m.xcol, (size_t)B * (m.cross_depth + 1)))) return st;
+  if ((m.type == RMX_MODEL_PNN || (m.type != RMX_MODEL_LR && needs_gather_x(m))) && (st = ensure_xbuf(m, B)))
+    return st;
   if (!m.cin_layers.empty()) {
     int maxH = 16;
     for (auto& c : m.cin_layers) maxH = std::max(maxH, c.Npad);
-    if ((st = dev_alloc(&m.ubuf[0], (size_t)B * m.k * maxH))) return st;
-    if ((st = dev_alloc(&m.ubuf[1], (size_t)B * m.k * maxH))) return st;
-    if ((st = dev_alloc(&m.rowdot, (size_t)B * m.k))) return st;
+    if ((st = ws_alloc(m, &m.ubuf[0], (size_t)B * m.k * maxH))) return st;
+    if ((st = ws_alloc(m, &m.ubuf[1], (size_t)B * m.k * maxH))) return st;
+    if ((st = ws_alloc(m, &m.rowdot, (size_t)B * m.k))) return st;
   }
   m.ws_B = B;
   return RMX_OK;
@@ -722,14 +759,20 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
   // that stream 1/13 of its split planes (k_gemm_s3.hip p.cols32), the output layer writing 13 partial logits
   // that out_finish_kernel sums in order with the head (layer 1 gathering its rows from the table instead of
   // the encoder's x measured slower: 0.031 vs 0.013 + 0.017 ms at B = 1,024, profiles/r06/ab_cols32_gather.txt).
-  // Auto choice only: s3_small 0 (the per-layer paths) and 2 (the whole-tower kernel, below) both bypass it
-  if (m.type == RMX_MODEL_DEEPFM && in.ids && !in.y1 && in.dtype == kF32 && !needs_gather_x(m) && k == 16 &&
-      B <= tuning_get("s3_cols", kS3ColsMaxB) && tuning_get("s3_small", 1) == 1 && m.xbuf && m.layers.size() >= 2 &&
-      m.layers[0].W3 && f32_split_enabled() && m.layers[0].Kpad == F * k) {
+  // Auto choice only: s3_small 0 (the per-layer paths) and 2 (the whole-tower kernel, below) both bypass it.
+  // The choice depends on this call's B, the knobs and the model alone: xbuf is grown here, not with the
+  // workspace.  The L-A staged rows (in.ids == nullptr, a regular index) take it too: la_E already is
+  // x = [B][F k], so layer 1 reads it in place and the encoder (implicit ids) only writes y1 + y2 -- the same
+  // sums in the same order as with ids, hence the same bits from rmx_forward and rmx_forward_ids
+  if (m.type == RMX_MODEL_DEEPFM && !in.y1 && in.dtype == kF32 && !needs_gather_x(m) && k == 16 &&
+      (in.ids || in.ld == 0 || in.ld == k) && B <= tuning_get("s3_cols", kS3ColsMaxB) &&
+      tuning_get("s3_small", 1) == 1 && m.layers.size() >= 2 && m.layers[0].W3 && f32_split_enabled() &&
+      m.layers[0].Kpad == F * k) {
+    if (in.ids && (st = ensure_xbuf(m, B))) return st;
     {
       StageTimer t(m, s, "encoder_fm_x");
       if ((st = launch_encoder(s, 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr, nullptr, in.ld,
-                               in.wld, m.xbuf)))
+                               in.wld, in.ids ? m.xbuf : nullptr)))
         return st;
     }
     OutArgs oa{};
@@ -740,7 +783,7 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
     oa.beta = in.beta;
     oa.out = in.out;
     oa.part = m.opart;
-    const float* A = m.xbuf;
+    const float* A = in.ids ? m.xbuf : (const float*)in.table;
     int lda = F * k;
     static const char* lnames[] = {"tower_layer1", "tower_layer2", "tower_layer3", "tower_layer4+"};
     for (size_t i = 0; i < m.layers.size(); ++i) {
@@ -940,17 +983,17 @@ int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, boo
   int st;
   if (nnz > m.la_nnz) {
     RMX_HIP(hipDeviceSynchronize());
-    dev_free(m.la_E);
-    dev_free(m.la_w);
-    if (m.type != RMX_MODEL_LR && (st = dev_alloc(&m.la_E, (size_t)nnz * m.k))) return st;
-    if ((st = dev_alloc(&m.la_w, nnz))) return st;
+    ws_free(m, m.la_E);
+    ws_free(m, m.la_w);
+    if (m.type != RMX_MODEL_LR && (st = ws_alloc(m, &m.la_E, (size_t)nnz * m.k))) return st;
+    if ((st = ws_alloc(m, &m.la_w, nnz))) return st;
     m.la_nnz = nnz;
   }
   if (B > m.la_B) {
     RMX_HIP(hipDeviceSynchronize());
-    dev_free(m.la_out);
-    dev_free(m.la_rowptr);
-    if ((st = dev_alloc(&m.la_out, B))) return st;
+    ws_free(m, m.la_out);
+    dev_free(m.la_rowptr);  // (row pointers: never in the scratch list, a leftover there would be an address)
+    if ((st = ws_alloc(m, &m.la_out, B))) return st;
     if (hipMalloc(&m.la_rowptr, sizeof(int64_t) * (B + 1)) != hipSuccess) {
       set_error("out of device memory");
       return RMX_E_NOMEM;
@@ -993,13 +1036,16 @@ int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, boo
     // (la_w in place too, so the Scatter first order below sums the rounded weights)
     if (nnz * std::max(m.k, 1) > m.la16_cap) {
       RMX_HIP(hipDeviceSynchronize());
-      dev_free(m.la_E16);
-      dev_free(m.la_w16);
+      ws_free(m, m.la_E16);
+      ws_free(m, m.la_w16);
+      m.la16_cap = 0;
       if (hipMalloc(&m.la_E16, sizeof(bf16_t) * nnz * std::max(m.k, 1)) != hipSuccess ||
           hipMalloc(&m.la_w16, sizeof(bf16_t) * nnz) != hipSuccess) {
         set_error("out of device memory");
         return RMX_E_NOMEM;
       }
+      scratch_note(m, m.la_E16, sizeof(bf16_t) * nnz * std::max(m.k, 1));
+      scratch_note(m, m.la_w16, sizeof(bf16_t) * nnz);
       m.la16_cap = nnz * std::max(m.k, 1);
     }
     if (m.type != RMX_MODEL_LR && (st = launch_convert_bf16(s, m.la_E, nnz * m.k, m.la_E16))) return st;

@@ -115,11 +115,16 @@ struct rmx_model {
   bool beta_set = false;
 
   // ---- workspace (grown on demand) ----
+  // every floating-point scratch buffer below, of the L-A staging and of TrainState, with its allocated size
+  // (rmx::scratch_note at the allocation, scratch_forget at the free): what rmx_debug_poison_workspace fills
+  struct Scratch { void* ptr; size_t bytes; };
+  std::vector<Scratch> scratch;
   int ws_B = 0;
+  int xbuf_B = 0;                     // xbuf's own capacity (rows): grown where a path that needs it is chosen
   float* h[2] = {nullptr, nullptr};   // [B][Npad] tower activations
   float* y12 = nullptr;               // [B] first order (+ FM)
   float* pre2 = nullptr;              // [B] model-specific additive term (CIN / cross)
-  float* xbuf = nullptr;              // [B][Kpad0] materialised A (PNN [x | ip], generic k)
+  float* xbuf = nullptr;              // [xbuf_B][Kpad0] materialised A (PNN [x | ip], generic k, DeepFM column-split x)
   float* ubuf[2] = {nullptr, nullptr};  // [B*k][Npad] CIN maps
   float* rowdot = nullptr;            // [B*k] CIN per-row output partials
   float* opart = nullptr;             // [slices][B] partial logits of a column-sliced output layer
@@ -179,6 +184,8 @@ int model_forward_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, b
                        float* out);
 int model_collect_timing(rmx_model& m);
 int model_ensure_ws(rmx_model& m, int B);  // inference workspace (y12, h, ...) for batches <= B
+void scratch_note(rmx_model& m, void* p, size_t bytes);
+void scratch_forget(rmx_model& m, void* p);
 int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, bool regular, bool sorted,
                      float bias, const float* weights, const float* embedding, const float* mats, FwdInputs* in);
 

@@ -31,6 +31,7 @@
 namespace rmx {
 
 struct TrainState {
+  rmx_model* owner = nullptr;   // (its scratch list records every buffer below but ones / onesR)
   int B = 0;
   int ldx = 0;                  // row stride of x / dx
   float* x = nullptr;           // [B][ldx] tower input (Reshape(B, F*k) of the gathered rows)
@@ -81,6 +82,20 @@ int talloc(float** p, size_t n) {
     return RMX_E_NOMEM;
   }
   return RMX_OK;
+}
+
+// scratch of the backward: allocated and recorded in the model's scratch list (rmx_debug_poison_workspace) /
+// forgotten and freed.  ones / onesR are written once at allocation and keep plain talloc / tfree
+int salloc(rmx_model& m, float** p, size_t n) {
+  const int st = talloc(p, n);
+  if (st == RMX_OK) scratch_note(m, *p, sizeof(float) * std::max<size_t>(n, 1));
+  return st;
+}
+
+template <class T>
+void sfree(rmx_model& m, T*& p) {
+  scratch_forget(m, p);
+  tfree(p);
 }
 
 __global__ void fill_kernel(int n, float v, float* __restrict__ y) {
@@ -1356,8 +1371,9 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 int ensure_part(TrainState& T, int64_t n) {
   if (n <= T.cap_part) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
-  tfree(T.part2);
-  int st = talloc(&T.part2, (size_t)n);
+  sfree(*T.owner, T.part2);
+  T.cap_part = 0;
+  int st = salloc(*T.owner, &T.part2, (size_t)n);
   if (st) return st;
   T.cap_part = n;
   return RMX_OK;
@@ -1587,64 +1603,67 @@ int colsum(TrainState& T, hipStream_t s, int rows, int N, const float* M, int ld
 // output columns of a tower layer that belong to the layer (DCN fused extra columns excluded)
 inline int eff_n(const DenseLayer& L) { return L.N1 >= 0 ? L.N1 : L.N; }
 
-int ensure_train(rmx_model& m, int B) {
+// s: the call's stream.  ones / onesR are filled on it, so the kernels of model_train that read them (queued on
+// the same stream) are ordered after the fill; the context's stream is non-blocking and orders nothing for a
+// caller's own stream
+int ensure_train(rmx_model& m, int B, hipStream_t s) {
   if (!m.train) m.train = new TrainState();
   TrainState& T = *m.train;
+  T.owner = &m;
   if (B <= T.B) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
-  tfree(T.x);
-  for (auto& p : T.h) tfree(p);
+  sfree(m, T.x);
+  for (auto& p : T.h) sfree(m, p);
   T.h.clear();
-  for (size_t i = 1; i < T.hm.size(); ++i) tfree(T.hm[i]);  // (hm[0] is borrowed from fms, never owned)
+  for (size_t i = 1; i < T.hm.size(); ++i) sfree(m, T.hm[i]);  // (hm[0] is borrowed from fms, never owned)
   T.hm.clear();
   T.hm_ok.clear();
-  tfree(T.g[0]);
-  tfree(T.g[1]);
-  tfree(T.fms);
-  tfree(T.p);
-  tfree(T.dz);
+  sfree(m, T.g[0]);
+  sfree(m, T.g[1]);
+  sfree(m, T.fms);
+  sfree(m, T.p);
+  sfree(m, T.dz);
   tfree(T.ones);
-  tfree(T.tmp);
-  tfree(T.xcol);
-  tfree(T.wc);
-  tfree(T.coef);
-  tfree(T.cst);
-  tfree(T.gwc);
-  for (auto& p : T.u) tfree(p);
+  sfree(m, T.tmp);
+  sfree(m, T.xcol);
+  sfree(m, T.wc);
+  sfree(m, T.coef);
+  sfree(m, T.cst);
+  sfree(m, T.gwc);
+  for (auto& p : T.u) sfree(m, p);
   T.u.clear();
-  tfree(T.x0);
-  tfree(T.gx0);
-  tfree(T.gu[0]);
-  tfree(T.gu[1]);
-  tfree(T.gpre);
-  tfree(T.dzr);
-  tfree(T.zb);
+  sfree(m, T.x0);
+  sfree(m, T.gx0);
+  sfree(m, T.gu[0]);
+  sfree(m, T.gu[1]);
+  sfree(m, T.gpre);
+  sfree(m, T.dzr);
+  sfree(m, T.zb);
   tfree(T.onesR);
-  tfree(T.part2);
+  sfree(m, T.part2);
   T.cap_part = 0;
-  if (T.part) (void)hipFree(T.part);
-  T.part = nullptr;
+  sfree(m, T.part);
   int st;
   T.ldx = m.layers.empty() ? 0 : m.layers[0].Kpad;
   int maxld = std::max(T.ldx, 16);
-  if (!m.layers.empty() && (st = talloc(&T.x, (size_t)B * T.ldx))) return st;
+  if (!m.layers.empty() && (st = salloc(m, &T.x, (size_t)B * T.ldx))) return st;
   for (auto& L : m.layers) {
     T.h.push_back(nullptr);
-    if ((st = talloc(&T.h.back(), (size_t)B * L.Npad))) return st;
+    if ((st = salloc(m, &T.h.back(), (size_t)B * L.Npad))) return st;
     T.hm.push_back(nullptr);
     T.hm_ok.push_back(0);
     // (layer 1's bits, from the training head, live in T.fms's second half)
-    if (T.h.size() > 1 && L.N == 400 && L.Npad == 416 && (st = talloc(&T.hm.back(), (size_t)B * 16))) return st;
+    if (T.h.size() > 1 && L.N == 400 && L.Npad == 416 && (st = salloc(m, &T.hm.back(), (size_t)B * 16))) return st;
     maxld = std::max(maxld, L.Npad);
   }
   if (!m.layers.empty()) {
-    if ((st = talloc(&T.g[0], (size_t)B * maxld))) return st;
-    if ((st = talloc(&T.g[1], (size_t)B * maxld))) return st;
+    if ((st = salloc(m, &T.g[0], (size_t)B * maxld))) return st;
+    if ((st = salloc(m, &T.g[1], (size_t)B * maxld))) return st;
   }
-  if ((st = talloc(&T.p, B)) || (st = talloc(&T.dz, B)) || (st = talloc(&T.ones, B))) return st;
+  if ((st = salloc(m, &T.p, B)) || (st = salloc(m, &T.dz, B)) || (st = talloc(&T.ones, B))) return st;
   // [2][B][16]: the FM sums, then (training head, k_head_s3.hip XS) h1's ReLU mask bits
-  if (m.type == RMX_MODEL_DEEPFM && m.k == 16 && (st = talloc(&T.fms, (size_t)B * 32))) return st;
-  if ((st = talloc(&T.tmp, std::max(maxld, 2 * m.cross_depth + 1)))) return st;
+  if (m.type == RMX_MODEL_DEEPFM && m.k == 16 && (st = salloc(m, &T.fms, (size_t)B * 32))) return st;
+  if ((st = salloc(m, &T.tmp, std::max(maxld, 2 * m.cross_depth + 1)))) return st;
   if (m.type == RMX_MODEL_XDEEPFM) {
     const int64_t R = (int64_t)B * m.k;
     int maxH = 16, maxFH = 16;
@@ -1654,30 +1673,31 @@ int ensure_train(rmx_model& m, int B) {
     }
     for (auto& c : m.cin_layers) {
       T.u.push_back(nullptr);
-      if ((st = talloc(&T.u.back(), (size_t)R * c.Npad))) return st;
+      if ((st = salloc(m, &T.u.back(), (size_t)R * c.Npad))) return st;
     }
     const int64_t budget = 64ll << 20;  // floats of the Z chunk (256 MB)
     T.rc = (int)std::min<int64_t>(R, std::max<int64_t>(m.k, budget / maxFH / m.k * m.k));
-    if ((st = talloc(&T.x0, (size_t)R * m.F)) || (st = talloc(&T.gx0, (size_t)R * m.F)) ||
-        (st = talloc(&T.gu[0], (size_t)R * maxH)) || (st = talloc(&T.gu[1], (size_t)R * maxH)) ||
-        (st = talloc(&T.gpre, (size_t)R * maxH)) || (st = talloc(&T.dzr, R)) ||
-        (st = talloc(&T.zb, (size_t)T.rc * maxFH)) || (st = talloc(&T.onesR, R)))
+    if ((st = salloc(m, &T.x0, (size_t)R * m.F)) || (st = salloc(m, &T.gx0, (size_t)R * m.F)) ||
+        (st = salloc(m, &T.gu[0], (size_t)R * maxH)) || (st = salloc(m, &T.gu[1], (size_t)R * maxH)) ||
+        (st = salloc(m, &T.gpre, (size_t)R * maxH)) || (st = salloc(m, &T.dzr, R)) ||
+        (st = salloc(m, &T.zb, (size_t)T.rc * maxFH)) || (st = talloc(&T.onesR, R)))
       return st;
-    hipLaunchKernelGGL(fill_kernel, dim3(nblk(R)), dim3(256), 0, m.ctx->stream, (int)R, 1.0f, T.onesR);
+    hipLaunchKernelGGL(fill_kernel, dim3(nblk(R)), dim3(256), 0, s, (int)R, 1.0f, T.onesR);
     RMX_HIP(hipGetLastError());
   }
   if (m.type == RMX_MODEL_DCN) {
     const int L = m.cross_depth, D = m.F * m.k;
-    if ((st = talloc(&T.xcol, (size_t)B * (L + 1))) || (st = talloc(&T.wc, (size_t)(L + 1) * D)) ||
-        (st = talloc(&T.coef, (size_t)B * (L + 1))) || (st = talloc(&T.cst, (size_t)B * (2 * L + 1))) ||
-        (st = talloc(&T.gwc, (size_t)(L + 1) * D)))
+    if ((st = salloc(m, &T.xcol, (size_t)B * (L + 1))) || (st = salloc(m, &T.wc, (size_t)(L + 1) * D)) ||
+        (st = salloc(m, &T.coef, (size_t)B * (L + 1))) || (st = salloc(m, &T.cst, (size_t)B * (2 * L + 1))) ||
+        (st = salloc(m, &T.gwc, (size_t)(L + 1) * D)))
       return st;
   }
   if (hipMalloc(&T.part, sizeof(double) * 2 * kMaxParts) != hipSuccess) {
     set_error("backward: out of device memory");
     return RMX_E_NOMEM;
   }
-  hipLaunchKernelGGL(fill_kernel, dim3(nblk(B)), dim3(256), 0, m.ctx->stream, B, 1.0f, T.ones);
+  scratch_note(m, T.part, sizeof(double) * 2 * kMaxParts);
+  hipLaunchKernelGGL(fill_kernel, dim3(nblk(B)), dim3(256), 0, s, B, 1.0f, T.ones);
   RMX_HIP(hipGetLastError());
   T.B = B;
   return RMX_OK;
@@ -1689,32 +1709,32 @@ void train_release(rmx_model& m) {
   if (!m.train) return;
   TrainState& T = *m.train;
   (void)hipDeviceSynchronize();
-  tfree(T.x);
-  for (auto& p : T.h) tfree(p);
-  for (size_t i = 1; i < T.hm.size(); ++i) tfree(T.hm[i]);  // (hm[0] is borrowed from fms, never owned)
-  tfree(T.g[0]);
-  tfree(T.g[1]);
-  tfree(T.fms);
-  tfree(T.p);
-  tfree(T.dz);
+  sfree(m, T.x);
+  for (auto& p : T.h) sfree(m, p);
+  for (size_t i = 1; i < T.hm.size(); ++i) sfree(m, T.hm[i]);  // (hm[0] is borrowed from fms, never owned)
+  sfree(m, T.g[0]);
+  sfree(m, T.g[1]);
+  sfree(m, T.fms);
+  sfree(m, T.p);
+  sfree(m, T.dz);
   tfree(T.ones);
-  tfree(T.tmp);
-  tfree(T.xcol);
-  tfree(T.wc);
-  tfree(T.coef);
-  tfree(T.cst);
-  tfree(T.gwc);
-  for (auto& p : T.u) tfree(p);
-  tfree(T.x0);
-  tfree(T.gx0);
-  tfree(T.gu[0]);
-  tfree(T.gu[1]);
-  tfree(T.gpre);
-  tfree(T.dzr);
-  tfree(T.zb);
+  sfree(m, T.tmp);
+  sfree(m, T.xcol);
+  sfree(m, T.wc);
+  sfree(m, T.coef);
+  sfree(m, T.cst);
+  sfree(m, T.gwc);
+  for (auto& p : T.u) sfree(m, p);
+  sfree(m, T.x0);
+  sfree(m, T.gx0);
+  sfree(m, T.gu[0]);
+  sfree(m, T.gu[1]);
+  sfree(m, T.gpre);
+  sfree(m, T.dzr);
+  sfree(m, T.zb);
   tfree(T.onesR);
-  tfree(T.part2);
-  if (T.part) (void)hipFree(T.part);
+  sfree(m, T.part2);
+  sfree(m, T.part);
   delete m.train;
   m.train = nullptr;
 }
@@ -1737,7 +1757,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
   if (B <= 0) return RMX_OK;
   int st = model_ensure_ws(m, B);  // y12 (first order + FM) lives in the inference workspace
   if (st) return st;
-  if ((st = ensure_train(m, B))) return st;
+  if ((st = ensure_train(m, B, s))) return st;
   if (m.timing) ++m.timed_calls;
   TrainState& T = *m.train;
   const int F = m.F, k = m.k, D = F * k, Lc = m.cross_depth;

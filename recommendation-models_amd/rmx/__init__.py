@@ -439,6 +439,17 @@ def debug_fill_lds(ctx, pattern=0x7FC00000, stream=None):
     check(_lib.lib.rmx_debug_fill_lds(ctx.handle, int(pattern) & 0xFFFFFFFF, stream))
 
 
+def debug_poison_workspace(model, pattern=0x7FC07FC0, stream=None):
+    """Test hook: fill the model's floating-point scratch buffers in HBM (inference workspace, L-A staging,
+    backward state; each over its whole allocated capacity) with a 32-bit pattern on the stream.  Returns the
+    number of bytes filled: 0 for a model that has never run."""
+    n = ctypes.c_int64(0)
+    # (a model that has made no device call yet has only its host-side handle: nothing to fill, no GPU touched)
+    h = model._dev if model._dev is not None else model._meta
+    check(_lib.lib.rmx_debug_poison_workspace(h, int(pattern) & 0xFFFFFFFF, stream, ctypes.byref(n)))
+    return int(n.value)
+
+
 # ------------------------------------------------------------------ models ---
 class RecModel:
     """abstract class RecModel(type) -- yr/model/RecModel.scala:6-127."""

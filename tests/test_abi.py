@@ -121,6 +121,20 @@ def test_sample_parser_libsvm_libffm():
     assert fields.tolist() == [0, 2] and coo.getColIndices().tolist() == [4, 8]
 
 
+def test_poison_workspace_never_run_and_null_model():
+    """rmx_debug_poison_workspace: a model that has never run owns no scratch -- RMX_OK, 0 bytes and no device
+    call (this test runs without a GPU); a NULL model is RMX_E_INVALID."""
+    m = rmx.DeepFM(1000, 39, 16, [400, 400, 400])
+    assert rmx.debug_poison_workspace(m, 0x7FC07FC0) == 0
+    n = ctypes.c_int64(-1)
+    assert _lib.lib.rmx_debug_poison_workspace(m._meta, 0x3F803F80, None, ctypes.byref(n)) == _lib.RMX_OK
+    assert n.value == 0
+    assert _lib.lib.rmx_debug_poison_workspace(m._meta, 0, None, None) == _lib.RMX_OK  # bytes_filled is nullable
+    n.value = -1
+    assert _lib.lib.rmx_debug_poison_workspace(None, 0x7FC07FC0, None, ctypes.byref(n)) == _lib.RMX_E_INVALID
+    assert b"NULL model" in _lib.lib.rmx_last_error()
+
+
 def test_wgrad_slice_count_pinned_for_the_bench_shapes():
     """the 208 x 208 dW's slice count S sets the fp32 summation order of the weight gradient.
     It is a pure function of (rows, N, K, CU count) with constants fixed in the source, pinned here for
