@@ -199,6 +199,62 @@ int rmx_backward_ids(rmx_model* m, const rmx_table* t, int32_t batch, const int3
                      const float* d_targets, float* d_g_bias, float* d_g_weights, float* d_g_embedding,
                      float* d_g_mats, float* d_loss, void* stream);
 
+/* ------------------------------------------------------------ optimiser ---- */
+/* Device-resident optimiser step: what the reference's optimize() does after the backward
+ * (ParRecModel.scala:439-478): sum the per-nonzero gradients per distinct id (makeWeightsGrad /
+ * makeEmbeddingGrad, :293-328) and push them through an optimiser (pushWeightBiasEmbeddingMats, :225-253,
+ * optim/Async{SGD,Momentum,Adagrad,Adam}.scala), on the table rows, mats and the global bias in place.
+ * hyper[n_hyper]: the kind's hyper-parameters in the order shown; trailing ones left out take the defaults
+ * shown (the reference's constructor defaults); eta has none.  All arithmetic is fp32 on the device, g the
+ * aggregated gradient, t the optimiser's step count (1 on the first apply, the same for every group):
+ *   SGD       p -= eta g
+ *   Momentum  v = momentum v + g;  p -= eta v
+ *   Adagrad   s = factor s + (1 - factor) g^2;  p -= eta g / (sqrt(s) + eps)
+ *   Adam      m = beta m + (1 - beta) g;  v = gamma v + (1 - gamma) g^2;
+ *             p -= eta (m / (1 - beta^t)) / (sqrt(v / (1 - gamma^t)) + eps)      (the powers: host, double)
+ * No weight decay.  The reference's shared numUpdates counter, which one push bumps once per pushed group (so
+ * its groups see different step counts), is deliberately NOT reproduced: Angel's server-side optimiser
+ * math is not part of the reference tree, and one step count per apply is the textbook form the tests pin.
+ * Sparse semantics (Angel's sparse PSF update): only rows whose id occurs in the batch change, parameters and
+ * state alike; every other row keeps its bits.  State: zero-initialised slots allocated at create (SGD 0,
+ * Momentum / Adagrad 1, Adam 2 per parameter): [V][k] and [V] for the table, mats_len and 1 for mats and the
+ * bias; LR allocates no embedding state, DNN no first-order state.
+ * Summation order (a contract): an id's gradient is the fp32 sum of its nonzeros' gradients in ascending
+ * nonzero order starting from the first term (the reference's addTo loop, :316-322); a list of more than 512
+ * occurrences is summed in consecutive chunks of 512 in that order, and the chunk sums are then added in chunk
+ * order.  No float atomics: results are bitwise repeatable and independent of the launch geometry.  Ids outside
+ * [0, V) are skipped and never addressed.
+ * fp32 models and fp32 tables only (RMX_E_INVALID otherwise; sharded tables are out of scope); host-only model,
+ * NULL arguments, unknown kind, a negative or non-finite eta: RMX_E_INVALID; table k != model k: RMX_E_SHAPE.
+ * Every check runs before any device call. */
+typedef struct rmx_optim rmx_optim;
+#define RMX_OPTIM_SGD 0       /* hyper: {eta}                         AsyncSGD(eta)                 */
+#define RMX_OPTIM_MOMENTUM 1  /* hyper: {eta, momentum=0.9}           AsyncMomentum                 */
+#define RMX_OPTIM_ADAGRAD 2   /* hyper: {eta, factor=0.9, eps=1e-7}   AsyncAdagrad (decayed squares)*/
+#define RMX_OPTIM_ADAM 3      /* hyper: {eta, gamma=0.99, beta=0.9, eps=1e-7}  AsyncAdam            */
+int rmx_optim_create(rmx_model* m, rmx_table* t, int kind, const double* hyper, int n_hyper, rmx_optim** out);
+int rmx_optim_destroy(rmx_optim* o);              /* before its model and table */
+int64_t rmx_optim_steps(const rmx_optim* o);
+/* Device pointers of state slot `slot` (0: v / s / m, 1: Adam's v), for debugging / parity only: [V], [V][k],
+ * [mats_len] and [1] floats; each output nullable; NULL where the optimiser holds no such state. */
+int rmx_optim_state_ptrs(const rmx_optim* o, int slot, void** d_weights, void** d_embedding, void** d_mats,
+                         void** d_bias);
+/* Apply one step from per-nonzero gradients in rmx_backward_ids' layout (each nullable = group untouched):
+ * d_ids [batch * nFields], d_g_bias [1], d_g_weights [batch * nFields], d_g_embedding [batch * nFields * k],
+ * d_g_mats [mats_len].  After the update of mats every packed form the forward and backward read is rebuilt
+ * from them on the stream, and a table's line copy (knob "table_lines") gets the touched rows too.
+ * Asynchronous on the stream, EXCEPT where the step changes a value the model keeps on the host, which is
+ * then refreshed with one small device-to-host copy and a stream synchronise: the global bias (every model,
+ * when d_g_bias is given); with d_g_mats, the output Linear's bias (DeepFM, DNN, PNN) and DCN's closed-form
+ * cross scalars.  (xDeepFM and LR with d_g_bias NULL stay asynchronous.) */
+int rmx_optim_apply(rmx_optim* o, int32_t batch, const int32_t* d_ids, const float* d_g_bias,
+                    const float* d_g_weights, const float* d_g_embedding, const float* d_g_mats, void* stream);
+/* backward into optimiser-owned buffers + apply; *loss (host, nullable) = mean BCE. Synchronous on return. */
+int rmx_train_step_ids(rmx_model* m, const rmx_table* t, rmx_optim* o, int32_t batch, const int32_t* d_ids,
+                       const float* d_targets, float* loss, void* stream);
+int rmx_model_get_mats(rmx_model* m, float* mats, int64_t n_mats);   /* D2H of the current mats */
+int rmx_model_get_bias(const rmx_model* m, float* bias);
+
 /* Predict loop over a device-resident row set (ParRecModel.predict*, ParRecModel.scala:519-581):
  * scores[r] for rows r < n_rows of ids [n_rows][F], forwards of `batch` rows. */
 int rmx_predict_ids(rmx_model* m, const rmx_table* t, int64_t n_rows, const int32_t* d_ids,

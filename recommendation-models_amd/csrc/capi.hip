@@ -647,6 +647,167 @@ extern "C" int rmx_backward_ids(rmx_model* m, const rmx_table* t, int32_t B, con
   return model_train(*m, s, in, o);
 }
 
+// ------------------------------------------------------------ optimiser --
+extern "C" int rmx_optim_create(rmx_model* m, rmx_table* t, int kind, const double* hyper, int n_hyper,
+                                rmx_optim** out) {
+  CHECK_ARG(out, "rmx_optim_create: out is NULL");
+  CHECK_ARG(m, "rmx_optim_create: model is NULL");
+  if (kind < RMX_OPTIM_SGD || kind > RMX_OPTIM_ADAM) {
+    set_error("rmx_optim_create: unknown optimiser kind " + std::to_string(kind));
+    return RMX_E_INVALID;
+  }
+  static const int kMaxHyper[4] = {1, 2, 3, 4};
+  CHECK_ARG(hyper && n_hyper >= 1, "rmx_optim_create: hyper needs at least eta");
+  if (n_hyper > kMaxHyper[kind]) {
+    set_error("rmx_optim_create: kind " + std::to_string(kind) + " takes at most " + std::to_string(kMaxHyper[kind]) +
+              " hyper-parameters, got " + std::to_string(n_hyper));
+    return RMX_E_INVALID;
+  }
+  for (int i = 0; i < n_hyper; ++i) CHECK_ARG(std::isfinite(hyper[i]), "rmx_optim_create: non-finite hyper-parameter");
+  CHECK_ARG(hyper[0] >= 0.0, "rmx_optim_create: eta is negative");
+  auto hp = [&](int i, double def) { return i < n_hyper ? hyper[i] : def; };
+  std::unique_ptr<rmx_optim> o(new rmx_optim());
+  o->kind = kind;
+  o->eta = hyper[0];
+  switch (kind) {
+    case RMX_OPTIM_MOMENTUM: o->a = hp(1, 0.9); o->nslots = 1; break;
+    case RMX_OPTIM_ADAGRAD: o->a = hp(1, 0.9); o->eps = hp(2, 1e-7); o->nslots = 1; break;
+    case RMX_OPTIM_ADAM: o->b = hp(1, 0.99); o->a = hp(2, 0.9); o->eps = hp(3, 1e-7); o->nslots = 2; break;
+    default: break;
+  }
+  CHECK_ARG(o->a >= 0.0 && o->a <= 1.0 && o->b >= 0.0 && o->b <= 1.0 && o->eps >= 0.0,
+            "rmx_optim_create: momentum / factor / gamma / beta must lie in [0, 1], eps must not be negative");
+  CHECK_ARG(kind != RMX_OPTIM_ADAM || (o->a < 1.0 && o->b < 1.0), "rmx_optim_create: Adam needs beta, gamma < 1");
+  CHECK_ARG(m->ctx, "rmx_optim_create: host-only model (created without a context)");
+  CHECK_ARG(t, "rmx_optim_create: table is NULL");
+  CHECK_ARG(m->precision == RMX_DTYPE_F32, "rmx_optim_create: fp32 models only");
+  CHECK_ARG(t->dtype == RMX_DTYPE_F32, "rmx_optim_create: fp32 tables only");
+  if (m->type != RMX_MODEL_LR && t->k != m->k) {
+    set_error("rmx_optim_create: table embedding_dim " + std::to_string(t->k) + " != model " + std::to_string(m->k));
+    return RMX_E_SHAPE;
+  }
+  o->m = m;
+  o->t = t;
+  o->upd_w = m->type != RMX_MODEL_DNN;
+  o->upd_e = m->type != RMX_MODEL_LR;
+  const int st = optim_alloc(*o);
+  if (st) return st;
+  *out = o.release();
+  return RMX_OK;
+}
+
+extern "C" int rmx_optim_destroy(rmx_optim* o) {
+  if (!o) return RMX_OK;
+  optim_release(*o);
+  delete o;
+  return RMX_OK;
+}
+
+extern "C" int64_t rmx_optim_steps(const rmx_optim* o) { return o ? o->steps : -1; }
+
+extern "C" int rmx_optim_state_ptrs(const rmx_optim* o, int slot, void** d_weights, void** d_embedding, void** d_mats,
+                                    void** d_bias) {
+  CHECK_ARG(o && slot >= 0 && slot < 2, "rmx_optim_state_ptrs: bad args");
+  const bool has = slot < o->nslots;
+  if (d_weights) *d_weights = has ? o->w_s[slot] : nullptr;
+  if (d_embedding) *d_embedding = has ? o->e_s[slot] : nullptr;
+  if (d_mats) *d_mats = has ? o->m_s[slot] : nullptr;
+  if (d_bias) *d_bias = has ? o->b_s + slot : nullptr;
+  return RMX_OK;
+}
+
+static int optim_ready(const char* who, rmx_optim* o, int32_t B, const int32_t* d_ids) {
+  if (!o || B < 0 || (!d_ids && B > 0)) {
+    set_error(std::string(who) + ": bad args");
+    return RMX_E_INVALID;
+  }
+  if (!o->m->params_ready && o->m->mats_len > 0) {
+    set_error(std::string(who) + ": call rmx_model_set_mats first");
+    return RMX_E_INVALID;
+  }
+  if (!o->m->beta_set) {
+    set_error(std::string(who) + ": call rmx_model_set_bias first");
+    return RMX_E_INVALID;
+  }
+  if (o->m->precision != RMX_DTYPE_F32) {
+    set_error(std::string(who) + ": fp32 models only");
+    return RMX_E_INVALID;
+  }
+  return RMX_OK;
+}
+
+extern "C" int rmx_optim_apply(rmx_optim* o, int32_t B, const int32_t* d_ids, const float* d_g_bias,
+                               const float* d_g_weights, const float* d_g_embedding, const float* d_g_mats,
+                               void* stream) {
+  int st = optim_ready("rmx_optim_apply", o, B, d_ids);
+  if (st) return st;
+  rmx_model* m = o->m;
+  RMX_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : m->ctx->stream;
+  ModelUse use(*m, s);
+  if (use.st) return use.st;
+  return optim_apply(*o, s, B, d_ids, d_g_bias, d_g_weights, d_g_embedding, d_g_mats, nullptr, nullptr, false);
+}
+
+extern "C" int rmx_train_step_ids(rmx_model* m, const rmx_table* t, rmx_optim* o, int32_t B, const int32_t* d_ids,
+                                  const float* d_targets, float* loss, void* stream) {
+  CHECK_ARG(m && t && o, "rmx_train_step_ids: bad args");
+  CHECK_ARG(o->m == m && o->t == t, "rmx_train_step_ids: the optimiser belongs to another model / table");
+  CHECK_ARG(d_targets || B == 0, "rmx_train_step_ids: targets is NULL");
+  int st = optim_ready("rmx_train_step_ids", o, B, d_ids);
+  if (st) return st;
+  RMX_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : m->ctx->stream;
+  ModelUse use(*m, s);
+  if (use.st) return use.st;
+  const int64_t nnz = (int64_t)B * m->F;
+  if ((st = optim_ensure_grads(*o, nnz))) return st;
+  FwdInputs in;
+  in.B = B;
+  in.ids = d_ids;
+  in.table = t->emb;
+  in.wtab = t->w;
+  in.dtype = t->dtype;
+  in.beta = m->beta;
+  TrainOutputs to;
+  to.targets = d_targets;
+  to.nnz = nnz;
+  to.g_bias = o->g_b;
+  to.g_w = o->g_w;
+  to.g_emb = o->g_e;
+  to.g_mats = o->g_m;
+  to.loss = o->g_b + 1;
+  if ((st = model_train(*m, s, in, to))) return st;
+  return optim_apply(*o, s, B, d_ids, o->g_b, o->g_w, o->g_e, o->g_m, o->g_b + 1, loss, true);
+}
+
+extern "C" int rmx_model_get_mats(rmx_model* m, float* mats, int64_t n) {
+  CHECK_ARG(m, "rmx_model_get_mats: model is NULL");
+  CHECK_ARG(m->ctx, "rmx_model_get_mats: host-only model (created without a context)");
+  if (n != m->mats_len) {
+    set_error("rmx_model_get_mats: mats has room for " + std::to_string(n) + " floats, the model has " +
+              std::to_string(m->mats_len));
+    return RMX_E_MATS;
+  }
+  if (m->mats_len > 0) CHECK_ARG(mats, "rmx_model_get_mats: mats is NULL");
+  CHECK_ARG(m->params_ready || m->mats_len == 0, "rmx_model_get_mats: call rmx_model_set_mats first");
+  RMX_HIP(hipSetDevice(m->ctx->device));
+  ModelUse use(*m, m->ctx->stream);  // after the last call's update of mats, whichever stream it ran on
+  if (use.st) return use.st;
+  if (m->mats_len > 0)
+    RMX_HIP(hipMemcpyAsync(mats, m->mats_dev, sizeof(float) * m->mats_len, hipMemcpyDeviceToHost, m->ctx->stream));
+  RMX_HIP(hipStreamSynchronize(m->ctx->stream));
+  return RMX_OK;
+}
+
+extern "C" int rmx_model_get_bias(const rmx_model* m, float* bias) {
+  CHECK_ARG(m && bias, "rmx_model_get_bias: bad args");
+  std::lock_guard<std::mutex> lk(const_cast<rmx_model*>(m)->mu);
+  CHECK_ARG(m->beta_set, "rmx_model_get_bias: call rmx_model_set_bias first");
+  *bias = m->beta;
+  return RMX_OK;
+}
+
 extern "C" int rmx_backward(rmx_model* m, int32_t B, int64_t nnz, const int64_t* index, const int64_t* feats,
                             float* bias, float* weights, float* embedding, int32_t embedding_dim, float* mats,
                             const int32_t* mat_sizes, int32_t n_sizes, const int64_t* fields, const float* targets,

@@ -550,13 +550,11 @@ int model_set_precision(rmx_model& m, int dtype) {
   return RMX_OK;
 }
 
-// Upload mats and pack every layer on the device (the reference rebuilds its BigDL modules
-// from mats on every call: LayerUtil.scala:13-19; here it is one H2D copy + pack kernels).
-int model_load_mats(rmx_model& m, const float* host_mats, bool sync) {
-  hipStream_t s = m.ctx->stream;
-  RMX_HIP(hipSetDevice(m.ctx->device));
-  if (m.mats_len > 0)
-    RMX_HIP(hipMemcpyAsync(m.mats_dev, host_mats, sizeof(float) * m.mats_len, hipMemcpyHostToDevice, s));
+// Every packed form the forward and the backward read, rebuilt on stream s from mats_dev (layer planes,
+// split-3 planes, transposes, CIN maps, wo, the DCN vectors): the device half of model_load_mats, and what
+// the optimiser runs after it has updated mats_dev in place (optim.hip).  The values the model keeps on the
+// host (bo, DCN cross_scalars) are the caller's to refresh.
+int model_repack(rmx_model& m, hipStream_t s) {
   int st;
   for (auto& L : m.layers) {
     if ((st = launch_pack_linear(s, m.mats_dev, L))) return st;
@@ -566,7 +564,6 @@ int model_load_mats(rmx_model& m, const float* host_mats, bool sync) {
   if (!m.layers.empty()) {
     const auto& last = m.layers.back();
     if ((st = copy_slice(s, m.mats_dev + m.wo_off, last.N, last.Npad, m.wo))) return st;
-    m.bo = m.has_bo ? host_mats[m.bo_off] : 0.f;
   }
   for (auto& c : m.cin_layers) {
     if ((st = launch_pack_cin(s, m.mats_dev, m.F, c))) return st;
@@ -579,6 +576,27 @@ int model_load_mats(rmx_model& m, const float* host_mats, bool sync) {
     if ((st = copy_slice(s, m.mats_dev + c.b_off, c.H, c.Npad, c.b))) return st;
     if ((st = copy_slice(s, m.mats_dev + c.wo_off, c.H, c.Npad, c.wo))) return st;
   }
+  if (m.type == RMX_MODEL_DCN) {
+    const int D = m.F * m.k;
+    RMX_HIP(hipMemcpyAsync(m.cross_w, m.mats_dev + m.cross_w_off, sizeof(float) * m.cross_depth * D,
+                           hipMemcpyDeviceToDevice, s));
+    RMX_HIP(hipMemcpyAsync(m.cross_b, m.mats_dev + m.cross_b_off, sizeof(float) * m.cross_depth,
+                           hipMemcpyDeviceToDevice, s));
+    RMX_HIP(hipMemcpyAsync(m.wo_x, m.mats_dev + m.wo_x_off, sizeof(float) * D, hipMemcpyDeviceToDevice, s));
+  }
+  return RMX_OK;
+}
+
+// Upload mats and pack every layer on the device (the reference rebuilds its BigDL modules
+// from mats on every call: LayerUtil.scala:13-19; here it is one H2D copy + pack kernels).
+int model_load_mats(rmx_model& m, const float* host_mats, bool sync) {
+  hipStream_t s = m.ctx->stream;
+  RMX_HIP(hipSetDevice(m.ctx->device));
+  if (m.mats_len > 0)
+    RMX_HIP(hipMemcpyAsync(m.mats_dev, host_mats, sizeof(float) * m.mats_len, hipMemcpyHostToDevice, s));
+  int st;
+  if ((st = model_repack(m, s))) return st;
+  if (!m.layers.empty()) m.bo = m.has_bo ? host_mats[m.bo_off] : 0.f;
   if (m.type == RMX_MODEL_DCN) {
     const int D = m.F * m.k;
     if (m.cross_depth <= kMaxFusedCross) {
@@ -595,11 +613,6 @@ int model_load_mats(rmx_model& m, const float* host_mats, bool sync) {
       for (int d = 0; d < D; ++d) wo += rv(host_mats[m.wo_x_off + d]);
       m.cross_scalars.wo_sum = (float)wo;
     }
-    RMX_HIP(hipMemcpyAsync(m.cross_w, m.mats_dev + m.cross_w_off, sizeof(float) * m.cross_depth * D,
-                           hipMemcpyDeviceToDevice, s));
-    RMX_HIP(hipMemcpyAsync(m.cross_b, m.mats_dev + m.cross_b_off, sizeof(float) * m.cross_depth,
-                           hipMemcpyDeviceToDevice, s));
-    RMX_HIP(hipMemcpyAsync(m.wo_x, m.mats_dev + m.wo_x_off, sizeof(float) * D, hipMemcpyDeviceToDevice, s));
   }
   if (sync) RMX_HIP(hipStreamSynchronize(s));
   m.params_ready = true;

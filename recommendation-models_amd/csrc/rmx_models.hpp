@@ -165,11 +165,50 @@ struct rmx_model {
   std::vector<hipEvent_t> ev_pool;
 };
 
+// Device-resident optimiser of one (model, table) pair (optim.hip): the state slots, the grouping scratch of
+// the sparse update and the gradient buffers of rmx_train_step_ids.  Used under its model's lock.
+struct rmx_optim {
+  rmx_model* m = nullptr;
+  rmx_table* t = nullptr;
+  int kind = 0;
+  double eta = 0, a = 0, b = 0, eps = 0;  // a: momentum / factor / beta; b: gamma (Adam)
+  int64_t steps = 0;
+  int nslots = 0;                  // state slots per parameter: SGD 0, Momentum / Adagrad 1, Adam 2
+  bool upd_w = false, upd_e = false;  // first order (not DNN) / embeddings (not LR)
+  float* w_s[2] = {nullptr, nullptr};   // [V]      per slot
+  float* e_s[2] = {nullptr, nullptr};   // [V][k]   per slot
+  float* m_s[2] = {nullptr, nullptr};   // [mats_len] per slot
+  float* b_s = nullptr;                 // [2] bias slots
+  float* hv = nullptr;                  // [rmx::kOptimHostVals] staging of the model's host-side values
+  // grouping scratch, grown on demand (every word read by an apply is written by it first)
+  int64_t cap_nnz = 0;
+  uint32_t* keys[2] = {nullptr, nullptr};
+  uint32_t* vals[2] = {nullptr, nullptr};
+  uint32_t* hist = nullptr;             // [256][tiles]
+  uint32_t* bsum = nullptr;             // sums of hist's 1,024-element blocks (the scan's first pass)
+  float* part = nullptr;                // [2 * windows][k + 1] chunk sums of lists longer than 512
+  int32_t* long_head = nullptr;         // [windows] start of the long list whose first chunk begins there
+  // rmx_train_step_ids' gradients
+  int64_t g_nnz = 0;
+  float *g_b = nullptr, *g_w = nullptr, *g_e = nullptr, *g_m = nullptr;  // g_b: [2] = {g_bias, loss}
+};
+
 namespace rmx {
+constexpr int kOptimHostVals = 4 + 2 * kMaxFusedCross;  // beta, bo, wsum[L], beta_l[L], wo_sum, loss
+int optim_alloc(rmx_optim& o);    // state slots (zero) after the argument checks
+void optim_release(rmx_optim& o);
+// One step from per-nonzero gradients (each nullable), the model's lock held by the caller.  Synchronises the
+// stream when the model keeps a value on the host that the step changed (the global bias; bo; DCN's
+// cross_scalars) or when sync is set; *loss (host, nullable) then receives loss_dev[0].
+int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias, const float* g_w,
+                const float* g_emb, const float* g_mats, const float* loss_dev, float* loss, bool sync);
+int optim_ensure_grads(rmx_optim& o, int64_t nnz);  // rmx_train_step_ids' gradient buffers for nnz nonzeros
 int model_build(rmx_model& m);
 void model_init_mats(const rmx_model& m, uint64_t seed, float* mats);
 void model_release(rmx_model& m);
 int model_load_mats(rmx_model& m, const float* host_mats, bool sync);
+// the packed forms rebuilt from mats_dev on stream s (no host values: bo / cross_scalars stay as they are)
+int model_repack(rmx_model& m, hipStream_t s);
 int model_set_precision(rmx_model& m, int dtype);
 int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in);
 // models whose every table read takes a row stride (DeepFM / DNN at k = 16, LR): they can read

@@ -24,7 +24,7 @@ import threading
 import weakref
 
 __all__ = ["RecModelType", "CooLongFloatMatrix", "RecModel", "LR", "DeepFM", "XDeepFM", "DCN", "PNN", "DNN",
-           "Context", "DeviceArray", "EmbeddingTable", "ShardedTable", "ExchangeGroup", "comm_unique_id", "SampleParser", "RmxError", "IllegalArgumentError",
+           "Context", "DeviceArray", "EmbeddingTable", "ShardedTable", "ExchangeGroup", "comm_unique_id", "Optimizer", "SampleParser", "RmxError", "IllegalArgumentError",
            "ShapeError", "MatsError", "default_context", "set_device", "shutdown"]
 
 MODEL_LR, MODEL_DEEPFM, MODEL_XDEEPFM, MODEL_DCN, MODEL_PNN, MODEL_DNN = range(6)
@@ -72,11 +72,11 @@ def get_tuning(key, default=0):
 
 # ------------------------------------------------------------- teardown ----
 # Every handle-owning object registers here.  shutdown() (an atexit hook) destroys the live ones in
-# dependency order -- sharded / plain tables, models, device buffers, exchange groups, then contexts --
+# dependency order -- optimisers, sharded / plain tables, models, device buffers, exchange groups, then contexts --
 # while the interpreter, librmx and the HIP runtime are all still up.  Left to __del__, they would be
 # freed during interpreter teardown, possibly after the HIP runtime's (or a profiler's) own exit
 # handlers (an exit-time SIGSEGV under rocprofv3).
-_LIVE_ORDER = ("shard", "table", "model", "array", "group", "ctx")
+_LIVE_ORDER = ("optim", "shard", "table", "model", "array", "group", "ctx")
 _live = {k: weakref.WeakSet() for k in _LIVE_ORDER}
 _shut = False
 
@@ -601,7 +601,29 @@ class RecModel:
         check(_lib.lib.rmx_backward_ids(self._device(), table.handle, int(batch), ids_dev.ptr, targets_dev.ptr,
                                         p(g_bias), p(g_weights), p(g_embedding), p(g_mats), p(loss), stream))
 
+    def train_step_ids(self, table, optim, batch, ids_dev, targets_dev, stream=None):
+        """One training step on the device (rmx_train_step_ids): the backward into the optimiser's own gradient
+        buffers, then its apply on the table rows, mats and the bias.  Synchronous; returns the mean BCE loss."""
+        if optim.model is not self or optim.table is not table:
+            raise IllegalArgumentError(_lib.RMX_E_INVALID, "train_step_ids: the optimiser belongs to another "
+                                       "model / table")
+        loss = ctypes.c_float()
+        check(_lib.lib.rmx_train_step_ids(self._device(), table.handle, optim.handle, int(batch), ids_dev.ptr,
+                                          targets_dev.ptr, ctypes.byref(loss), stream))
+        return loss.value
+
     # -- device-resident path (replaces ParRecModel.pull* + make*)
+    def getMats(self):
+        """The model's current mats (getMatsSize layout) copied back from the device (rmx_model_get_mats)."""
+        mats = np.zeros(self.matsLength(), np.float32)
+        check(_lib.lib.rmx_model_get_mats(self._device(), ptr(mats, ctypes.c_float), len(mats)))
+        return mats
+
+    def getBias(self):
+        b = ctypes.c_float()
+        check(_lib.lib.rmx_model_get_bias(self._device(), ctypes.byref(b)))
+        return b.value
+
     def setMats(self, mats):
         mats = np.ascontiguousarray(mats, np.float32)
         check(_lib.lib.rmx_model_set_mats(self._device(), ptr(mats, ctypes.c_float), len(mats)))
@@ -704,6 +726,68 @@ class PNN(RecModel):
 
     def __init__(self, inputDim, nFields, embeddingDim, fcDims, ctx=None):
         super().__init__(inputDim, nFields, embeddingDim, fcDims, ctx=ctx)
+
+
+# --------------------------------------------------------------- optimiser ---
+class Optimizer:
+    """Device-resident optimiser of one (model, table) pair (rmx_optim): per-id sums of the per-nonzero
+    gradients pushed through SGD / Momentum / Adagrad / Adam on the table rows, mats and the bias
+    (ParRecModel.optimize, ParRecModel.scala:439-478; formulas and the summation order: include/rmx.h).
+    kind: "sgd" (eta), "momentum" (eta, momentum=0.9), "adagrad" (eta, factor=0.9, eps=1e-7) or
+    "adam" (eta, gamma=0.99, beta=0.9, eps=1e-7), or the OPTIM_* number.  Keeps its model and table alive."""
+
+    KINDS = {"sgd": _lib.OPTIM_SGD, "momentum": _lib.OPTIM_MOMENTUM, "adagrad": _lib.OPTIM_ADAGRAD,
+             "adam": _lib.OPTIM_ADAM}
+    HYPER = {_lib.OPTIM_SGD: (("eta", None),),
+             _lib.OPTIM_MOMENTUM: (("eta", None), ("momentum", 0.9)),
+             _lib.OPTIM_ADAGRAD: (("eta", None), ("factor", 0.9), ("eps", 1e-7)),
+             _lib.OPTIM_ADAM: (("eta", None), ("gamma", 0.99), ("beta", 0.9), ("eps", 1e-7))}
+
+    def __init__(self, model, table, kind, **hyper):
+        if isinstance(kind, str):
+            if kind.lower() not in self.KINDS:
+                raise IllegalArgumentError(_lib.RMX_E_INVALID, "unknown optimiser kind %r" % (kind,))
+            kind = self.KINDS[kind.lower()]
+        names = self.HYPER.get(int(kind), (("eta", None),))
+        unknown = sorted(set(hyper) - {n for n, _ in names})
+        if unknown:
+            raise TypeError("optimiser kind %d takes no hyper-parameter %s" % (kind, ", ".join(unknown)))
+        if "eta" not in hyper:
+            raise TypeError("Optimizer: eta is required")
+        last = max(i for i, (n, _) in enumerate(names) if n in hyper)  # later ones take the library's defaults
+        vals = [float(hyper.get(n, d)) for n, d in names[:last + 1]]
+        arr = (ctypes.c_double * len(vals))(*vals)
+        h = ctypes.c_void_p()
+        check(_lib.lib.rmx_optim_create(model._device(), table.handle, int(kind), arr, len(vals), ctypes.byref(h)))
+        self.handle = h
+        self.model = model
+        self.table = table
+        self.kind = int(kind)
+        _track("optim", self)
+
+    @property
+    def steps(self):
+        return int(_lib.lib.rmx_optim_steps(self.handle)) if self.handle else 0
+
+    def apply(self, batch, ids_dev, g_bias=None, g_weights=None, g_embedding=None, g_mats=None, stream=None):
+        """One step from the per-nonzero gradients of backward_ids (DeviceArrays; None leaves the group
+        untouched)."""
+        if not self.handle:
+            raise RmxError(_lib.RMX_E_INVALID, "optimiser is closed")
+        p = lambda a: None if a is None else a.ptr
+        check(_lib.lib.rmx_optim_apply(self.handle, int(batch), ids_dev.ptr, p(g_bias), p(g_weights),
+                                       p(g_embedding), p(g_mats), stream))
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            _lib.lib.rmx_optim_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------------------------ parser ---

@@ -25,6 +25,7 @@ DTYPE_F32 = 0
 DTYPE_BF16 = 1
 LAYOUT_K_MAJOR = 0
 LAYOUT_ROW_MAJOR = 1
+OPTIM_SGD, OPTIM_MOMENTUM, OPTIM_ADAGRAD, OPTIM_ADAM = 0, 1, 2, 3
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -82,6 +83,14 @@ SIGNATURES = [
     ("rmx_backward", c_int, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp,
                              c_vp, c_vp]),
     ("rmx_backward_ids", c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("rmx_optim_create", c_int, [c_vp, c_vp, c_int, P(ctypes.c_double), c_int, P(c_vp)]),
+    ("rmx_optim_destroy", c_int, [c_vp]),
+    ("rmx_optim_steps", c_i64, [c_vp]),
+    ("rmx_optim_state_ptrs", c_int, [c_vp, c_int, P(c_vp), P(c_vp), P(c_vp), P(c_vp)]),
+    ("rmx_optim_apply", c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("rmx_train_step_ids", c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(c_f32), c_vp]),
+    ("rmx_model_get_mats", c_int, [c_vp, P(c_f32), c_i64]),
+    ("rmx_model_get_bias", c_int, [c_vp, P(c_f32)]),
     ("rmx_gen_ids", c_int, [c_vp, c_u64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp]),
     ("rmx_gen_ids_zipf", c_int, [c_vp, c_u64, c_i64, c_i32, c_i32, c_i64, ctypes.c_double, c_vp, c_vp]),
     ("rmx_debug_fill_lds", c_int, [c_vp, ctypes.c_uint32, c_vp]),
