@@ -284,6 +284,12 @@ int rmx_debug_fill_lds(rmx_ctx* ctx, uint32_t pattern, void* stream);
  * no device call.  NULL model: RMX_E_INVALID. */
 int rmx_debug_poison_workspace(rmx_model* model, uint32_t pattern, void* stream, int64_t* bytes_filled);
 
+/* Test hook (no device call): the device memory that the library's objects -- models, tables, optimisers,
+ * shards, a running rmx_auc -- hold right now in this process: *bytes and *buffers (each nullable).  Memory
+ * from rmx_malloc belongs to the caller and is not counted.  Both are back at their earlier reading once
+ * everything created since has been destroyed (tests/test_device_memory.py). */
+int rmx_debug_live_device_memory(int64_t* bytes, int64_t* buffers);
+
 /* Test hook (host only, no GPU): the slice count S the training dW on the 208 x 208 tile uses for a
  * rows x N x K weight gradient on a device with ncu CUs.  S fixes the dW's fp32 summation order over the
  * slices, so gradients are bitwise reproducible across devices with the same CU count (every 256-CU

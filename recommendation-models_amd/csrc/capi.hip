@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -20,6 +21,23 @@ namespace rmx {
 
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+
+// Every DevBuf's memory (dev_buf.hpp); the two counters are what rmx_debug_live_device_memory reports.
+static std::atomic<int64_t> g_live_bytes{0}, g_live_buffers{0};
+
+void* dev_raw_alloc(size_t bytes) {
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+  g_live_bytes += (int64_t)bytes;
+  ++g_live_buffers;
+  return p;
+}
+
+void dev_raw_free(void* p, size_t bytes) {
+  (void)hipFree(p);
+  g_live_bytes -= (int64_t)bytes;
+  --g_live_buffers;
+}
 
 static std::mutex g_tune_mu;
 static std::vector<std::pair<std::string, int>> g_tune;
@@ -280,19 +298,16 @@ extern "C" int rmx_table_create_ex(rmx_ctx* c, int64_t V, int k, int dtype, rmx_
   CHECK_ARG(V < (int64_t(1) << 31), "rmx_table_create: rows must fit int32 (ParRecModel.scala:282 .toInt)");
   CHECK_ARG(dtype == RMX_DTYPE_F32 || dtype == RMX_DTYPE_BF16, "rmx_table_create: dtype must be F32 or BF16");
   RMX_HIP(hipSetDevice(c->device));
-  auto* t = new rmx_table();
+  std::unique_ptr<rmx_table> t(new rmx_table());
   t->ctx = c;
   t->V = V;
   t->k = k;
   t->dtype = dtype;
   const size_t es = dtype_size(dtype);
-  if (hipMalloc(&t->w, es * V) != hipSuccess || (k > 0 && hipMalloc(&t->emb, es * V * k) != hipSuccess)) {
-    if (t->w) (void)hipFree(t->w);
-    delete t;
-    set_error("rmx_table_create: out of device memory");
-    return RMX_E_NOMEM;
-  }
-  *out = t;
+  int st = t->w.alloc(es * V, "rmx_table_create");
+  if (!st && k > 0) st = t->emb.alloc(es * V * k, "rmx_table_create");
+  if (st) return st;
+  *out = t.release();
   return RMX_OK;
 }
 
@@ -307,18 +322,15 @@ int rmx::table_refresh_lines(rmx_table& t) {
   if (!want) {
     if (t.line) {
       RMX_HIP(hipStreamSynchronize(t.ctx->stream));
-      (void)hipFree(t.line);
-      t.line = nullptr;
+      t.line.reset();
     }
     return RMX_OK;
   }
   const size_t es = t.dtype == RMX_DTYPE_BF16 ? sizeof(bf16_t) : sizeof(float);
-  if (!t.line && hipMalloc(&t.line, es * 32 * t.V) != hipSuccess) {
-    t.line = nullptr;
-    set_error("rmx_table: out of device memory for the line copy (set knob table_lines 0)");
-    return RMX_E_NOMEM;
-  }
-  const int st = launch_pack_lines(t.ctx->stream, t.V, t.emb, t.w, t.line, t.dtype);
+  int st;
+  if (!t.line && (st = t.line.alloc(es * 32 * t.V / sizeof(float), "rmx_table line copy (set knob table_lines 0)")))
+    return st;
+  st = launch_pack_lines(t.ctx->stream, t.V, t.emb, t.w, t.line, t.dtype);
   if (st) return st;
   RMX_HIP(hipStreamSynchronize(t.ctx->stream));
   return RMX_OK;
@@ -334,9 +346,6 @@ extern "C" int rmx_table_destroy(rmx_table* t) {
   if (!t) return RMX_OK;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
-  if (t->w) (void)hipFree(t->w);
-  if (t->emb) (void)hipFree(t->emb);
-  if (t->line) (void)hipFree(t->line);
   delete t;
   return RMX_OK;
 }
@@ -360,18 +369,15 @@ extern "C" int rmx_table_upload(rmx_table* t, const float* weights, const float*
   const bool bf = t->dtype == RMX_DTYPE_BF16;
   // fp32 host arrays; a bf16 table stores them rounded to nearest even on the device
   const size_t need = (size_t)t->V * std::max(1, bf || layout == RMX_LAYOUT_K_MAJOR ? t->k : 0);
-  float* tmp = nullptr;
-  if (bf || (emb && layout == RMX_LAYOUT_K_MAJOR)) {
-    if (hipMalloc(&tmp, sizeof(float) * std::max<size_t>(need, t->V)) != hipSuccess) {
-      set_error("rmx_table_upload: out of device memory for the staging copy");
-      return RMX_E_NOMEM;
-    }
-  }
+  DevBuf<float> tmp;
   int st = RMX_OK;
+  if ((bf || (emb && layout == RMX_LAYOUT_K_MAJOR)) &&
+      (st = tmp.alloc(std::max<size_t>(need, t->V), "rmx_table_upload (staging copy)")))
+    return st;
   if (weights) {
     if (bf) {
       RMX_HIP(hipMemcpyAsync(tmp, weights, sizeof(float) * t->V, hipMemcpyHostToDevice, s));
-      st = launch_convert_bf16(s, tmp, t->V, (bf16_t*)t->w);
+      st = launch_convert_bf16(s, tmp, t->V, (bf16_t*)t->w.get());
       RMX_HIP(hipStreamSynchronize(s));
     } else {
       RMX_HIP(hipMemcpyAsync(t->w, weights, sizeof(float) * t->V, hipMemcpyHostToDevice, s));
@@ -383,12 +389,12 @@ extern "C" int rmx_table_upload(rmx_table* t, const float* weights, const float*
       RMX_HIP(hipMemcpyAsync(t->emb, emb, bytes, hipMemcpyHostToDevice, s));
     } else {
       RMX_HIP(hipMemcpyAsync(tmp, emb, bytes, hipMemcpyHostToDevice, s));
-      st = layout == RMX_LAYOUT_ROW_MAJOR ? launch_convert_bf16(s, tmp, t->V * t->k, (bf16_t*)t->emb)
+      st = layout == RMX_LAYOUT_ROW_MAJOR ? launch_convert_bf16(s, tmp, t->V * t->k, (bf16_t*)t->emb.get())
                                           : launch_transpose_kmajor(s, tmp, t->V, t->k, t->emb, t->dtype);
     }
   }
   RMX_HIP(hipStreamSynchronize(s));
-  if (tmp) (void)hipFree(tmp);
+  tmp.reset();
   if (st == RMX_OK) st = table_refresh_lines(*t);
   return st;
 }
@@ -434,8 +440,8 @@ extern "C" int rmx_debug_fill_lds(rmx_ctx* c, uint32_t pattern, void* stream) {
 // allocated capacity (the high-water mark of the batches so far, not the last call's B), so a kernel of the
 // next call that reads a pad column or a row past B that the call did not write sees the pattern rather than
 // whatever the allocator or an earlier, larger batch left there.  The buffers are the ones recorded in
-// rmx_model::scratch where they are allocated: the inference workspace (h, y12, pre2, xcol, xbuf, ubuf, rowdot,
-// opart), the L-A staging (la_E, la_w, la_out, la_E16, la_w16) and the backward's TrainState (x, h, hm, g, fms,
+// rmx_model::scratch while they are allocated (the ScratchBuf members): the inference workspace (h, y12, pre2,
+// xcol, xbuf, ubuf, rowdot, opart), the L-A staging (la_E, la_w, la_out, la_E16, la_w16) and the backward's TrainState (x, h, hm, g, fms,
 // p, dz, tmp, xcol, wc, coef, cst, gwc, u, x0, gx0, gu, gpre, dzr, zb, part, part2).
 // Left out on purpose:
 //  - whatever holds indices, offsets or pointers (la_rowptr, the L-A backward's index copy, id buffers): a
@@ -464,6 +470,14 @@ extern "C" int rmx_debug_poison_workspace(rmx_model* m, uint32_t pattern, void* 
     total += (int64_t)(b.bytes & ~(size_t)1);
   }
   if (bytes_filled) *bytes_filled = total;
+  return RMX_OK;
+}
+
+// Test hook: device memory the library's objects hold right now, over the whole process (rmx_malloc's raw
+// pointers are the caller's and not counted).
+extern "C" int rmx_debug_live_device_memory(int64_t* bytes, int64_t* buffers) {
+  if (bytes) *bytes = g_live_bytes.load();
+  if (buffers) *buffers = g_live_buffers.load();
   return RMX_OK;
 }
 
@@ -836,18 +850,13 @@ extern "C" int rmx_backward(rmx_model* m, int32_t B, int64_t nnz, const int64_t*
   const bool use_w = m->type != RMX_MODEL_DNN, use_e = m->type != RMX_MODEL_LR;
   if (nnz > lb->nnz || B > lb->B || m->mats_len > lb->ml) {
     RMX_HIP(hipDeviceSynchronize());
-    for (void* p : {(void*)lb->gw, (void*)lb->ge, (void*)lb->gm, (void*)lb->gb, (void*)lb->tg, (void*)lb->idx})
-      if (p) (void)hipFree(p);
     *lb = rmx_model::LaGrad{};
-    const int64_t n1 = std::max<int64_t>(nnz, 1);
-    if (hipMalloc(&lb->gw, sizeof(float) * n1) != hipSuccess ||
-        hipMalloc(&lb->ge, sizeof(float) * n1 * std::max(m->k, 1)) != hipSuccess ||
-        hipMalloc(&lb->gm, sizeof(float) * std::max<int64_t>(m->mats_len, 1)) != hipSuccess ||
-        hipMalloc(&lb->gb, sizeof(float) * 2) != hipSuccess || hipMalloc(&lb->tg, sizeof(float) * B) != hipSuccess ||
-        hipMalloc(&lb->idx, sizeof(int32_t) * n1) != hipSuccess) {
-      set_error("rmx_backward: out of device memory");
-      return RMX_E_NOMEM;
-    }
+    const size_t n1 = (size_t)std::max<int64_t>(nnz, 1);
+    const char* who = "rmx_backward";
+    if ((st = lb->gw.alloc(n1, who)) || (st = lb->ge.alloc(n1 * std::max(m->k, 1), who)) ||
+        (st = lb->gm.alloc((size_t)m->mats_len, who)) || (st = lb->gb.alloc(2, who)) ||
+        (st = lb->tg.alloc(B, who)) || (st = lb->idx.alloc(n1, who)))
+      return st;
     lb->nnz = nnz;
     lb->B = B;
     lb->ml = m->mats_len;

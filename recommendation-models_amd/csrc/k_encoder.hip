@@ -518,7 +518,7 @@ int launch_convert_bf16(hipStream_t s, const float* src, int64_t n, bf16_t* dst)
 // W (out x in row-major at mats + w_off) -> [Kpad/16][Npad][16]; bias -> [Npad].
 // (PNN: columns >= K1 come from a second matrix at w_off2; bias_mode 2 broadcasts one scalar.)
 // value of W[n][kx] of a packed layer (PNN: two matrices side by side; DCN: extra cross rows)
-__device__ __forceinline__ float layer_w(const float* __restrict__ mats, const DenseLayer& L, int n, int kx) {
+__device__ __forceinline__ float layer_w(const float* __restrict__ mats, const LayerPlan& L, int n, int kx) {
   if (n >= L.N || kx >= L.K) return 0.f;
   if (L.N1 >= 0 && n >= L.N1) {
     const int e = n - L.N1;
@@ -529,7 +529,7 @@ __device__ __forceinline__ float layer_w(const float* __restrict__ mats, const D
   return mats[L.w_off2 + (int64_t)n * (L.K - L.K1) + (kx - L.K1)];
 }
 
-__global__ void pack_linear_kernel(const float* __restrict__ mats, DenseLayer L, int64_t b_off, int bias_mode,
+__global__ void pack_linear_kernel(const float* __restrict__ mats, LayerPlan L, int64_t b_off, int bias_mode,
                                    int K, int N, int Kpad, int Npad, float* __restrict__ Wp, float* __restrict__ bp) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t tot = (int64_t)Kpad * Npad;
@@ -551,7 +551,7 @@ __global__ void pack_linear_kernel(const float* __restrict__ mats, DenseLayer L,
 }
 
 // bf16 packing: [Kpad/32][Npad][32] (one 64-B row = 32 bf16 of one output column), RNE rounding
-__global__ void pack_linear_bf16_kernel(const float* __restrict__ mats, DenseLayer L, int Kpad, int Npad,
+__global__ void pack_linear_bf16_kernel(const float* __restrict__ mats, LayerPlan L, int Kpad, int Npad,
                                         bf16_t* __restrict__ Wp) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t tot = (int64_t)Kpad * Npad;

@@ -233,7 +233,7 @@ int launch_tower_layer(hipStream_t s, const DenseLayer& L, int M, const float* A
     }
     p.gsh = __builtin_ctz((unsigned)p.ga.ld);
   }
-  p.Wp = L.W16 ? reinterpret_cast<const float*>(L.W16) : L.W;
+  p.Wp = L.W16 ? reinterpret_cast<const float*>(L.W16.get()) : L.W;
   p.bias = L.b;
   p.C = C;
   p.ldc = ldc;
@@ -273,7 +273,7 @@ int launch_tower_layer(hipStream_t s, const DenseLayer& L, int M, const float* A
   }
   if (use_s3(L) && (epi != Epi::kOutput || L.Npad == kS3BN || oa->part)) {
     // fp32 layer on the bf16 matrix cores through the exact 3-way split (k_gemm_s3.hip)
-    p.Wp = reinterpret_cast<const float*>(L.W3);
+    p.Wp = reinterpret_cast<const float*>(L.W3.get());
     p.Kpad = (L.Kpad / 16 + 1) / 2 * 32;
     // cols32: DeepFM's column-split small-batch path (models.hip, knob "s3_cols") runs its dense-A layers on
     // 32-column blocks
@@ -326,7 +326,7 @@ int launch_cin_layer(hipStream_t s, const CinLayer& L, bool first, bool last, in
     return RMX_E_INVALID;
   }
   if (L.W3 && f32_split_enabled() && L.Npad == kS3BN) {
-    p.Wp = reinterpret_cast<const float*>(L.W3);
+    p.Wp = reinterpret_cast<const float*>(L.W3.get());
     p.cin_pair_hc = -1;
     if (L.map_on) {  // W3 packed in the chunk-map order (cin_chunk_map)
       p.K = L.ncm * 16;

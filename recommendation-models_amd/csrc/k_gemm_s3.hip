@@ -103,7 +103,7 @@ int launch_cin_dz_s3(hipStream_t s, const CinLayer& c, int rows, const float* gp
   p.Npad = c.NTpad;
   p.A = gpre;
   p.lda = ldg;
-  p.Wp = reinterpret_cast<const float*>(c.WT3);
+  p.Wp = reinterpret_cast<const float*>(c.WT3.get());
   p.bias = nullptr;
   p.C = dz;
   p.ldc = ldz;
@@ -129,7 +129,7 @@ int launch_dx_s3(hipStream_t s, const DenseLayer& L, int B, const float* dpre, i
   p.Npad = L.NTpad;
   p.A = dpre;
   p.lda = lda;
-  p.Wp = reinterpret_cast<const float*>(L.WT3);
+  p.Wp = reinterpret_cast<const float*>(L.WT3.get());
   p.bias = nullptr;
   p.C = dx;
   p.ldc = ldx;

@@ -53,21 +53,6 @@ __global__ __launch_bounds__(256) void auc_part_kernel(int runs, const int* __re
   if (threadIdx.x == 0) part[blockIdx.x] = sm[0];
 }
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)) != hipSuccess) {
-      set_error("auc: out of device memory");
-      return RMX_E_NOMEM;
-    }
-    return RMX_OK;
-  }
-};
-
 int device_auc(hipStream_t s, int64_t n64, const float* labels, const float* scores, double* auc) {
   if (n64 > 2147483647ll) {
     set_error("rmx_auc: at most 2^31 - 1 pairs");
@@ -82,61 +67,60 @@ int device_auc(hipStream_t s, int64_t n64, const float* labels, const float* sco
   DevBuf<long long> negb, negr64;
   DevBuf<double> part;
   int st;
-  if ((st = lab.alloc(n)) || (st = lab_s.alloc(n)) || (st = key_s.alloc(n)) || (st = uniq.alloc(n)) ||
-      (st = cnt.alloc(n + 1)) || (st = off.alloc(n + 1)) || (st = posr.alloc(n)) || (st = negr.alloc(n)) ||
-      (st = negb.alloc(n)) || (st = negr64.alloc(n)) || (st = nruns.alloc(1)))
+  const char* who = "auc";
+  if ((st = lab.alloc(n, who)) || (st = lab_s.alloc(n, who)) || (st = key_s.alloc(n, who)) ||
+      (st = uniq.alloc(n, who)) || (st = cnt.alloc(n + 1, who)) || (st = off.alloc(n + 1, who)) ||
+      (st = posr.alloc(n, who)) || (st = negr.alloc(n, who)) || (st = negb.alloc(n, who)) ||
+      (st = negr64.alloc(n, who)) || (st = nruns.alloc(1, who)))
     return st;
-  hipLaunchKernelGGL(label_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (int64_t)n, labels, lab.p);
+  hipLaunchKernelGGL(label_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (int64_t)n, labels, lab.get());
   RMX_HIP(hipGetLastError());
   // temp storage: the largest requirement of the primitives below
   size_t tb = 0, t;
-  RMX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t, scores, key_s.p, lab.p, lab_s.p, n, 0, 32, s));
+  RMX_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t, scores, key_s.get(), lab.get(), lab_s.get(), n, 0, 32, s));
   tb = std::max(tb, t);
-  RMX_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t, key_s.p, uniq.p, cnt.p, nruns.p, n, s));
+  RMX_HIP(hipcub::DeviceRunLengthEncode::Encode(nullptr, t, key_s.get(), uniq.get(), cnt.get(), nruns.get(), n, s));
   tb = std::max(tb, t);
-  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, cnt.p, off.p, n + 1, s));
+  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, cnt.get(), off.get(), n + 1, s));
   tb = std::max(tb, t);
-  RMX_HIP(hipcub::DeviceSegmentedReduce::Sum(nullptr, t, lab_s.p, posr.p, n, off.p, off.p + 1, s));
+  RMX_HIP(hipcub::DeviceSegmentedReduce::Sum(nullptr, t, lab_s.get(), posr.get(), n, off.get(), off.get() + 1, s));
   tb = std::max(tb, t);
-  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, negr64.p, negb.p, n, s));
+  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t, negr64.get(), negb.get(), n, s));
   tb = std::max(tb, t);
   DevBuf<unsigned char> tmp;
-  if (hipMalloc(&tmp.p, tb ? tb : 1) != hipSuccess) {
-    set_error("auc: out of device memory");
-    return RMX_E_NOMEM;
-  }
+  if ((st = tmp.alloc(tb, who))) return st;
   t = tb;
-  RMX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, t, scores, key_s.p, lab.p, lab_s.p, n, 0, 32, s));
+  RMX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.get(), t, scores, key_s.get(), lab.get(), lab_s.get(), n, 0, 32, s));
   t = tb;
-  RMX_HIP(hipcub::DeviceRunLengthEncode::Encode(tmp.p, t, key_s.p, uniq.p, cnt.p, nruns.p, n, s));
+  RMX_HIP(hipcub::DeviceRunLengthEncode::Encode(tmp.get(), t, key_s.get(), uniq.get(), cnt.get(), nruns.get(), n, s));
   int runs = 0;
-  RMX_HIP(hipMemcpyAsync(&runs, nruns.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  RMX_HIP(hipMemcpyAsync(&runs, nruns.get(), sizeof(int), hipMemcpyDeviceToHost, s));
   RMX_HIP(hipStreamSynchronize(s));
   // run offsets: exclusive scan of the run sizes with one trailing zero -> off[runs] = n
-  RMX_HIP(hipMemsetAsync(cnt.p + runs, 0, sizeof(int), s));
+  RMX_HIP(hipMemsetAsync(cnt.get() + runs, 0, sizeof(int), s));
   t = tb;
-  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, cnt.p, off.p, runs + 1, s));
+  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.get(), t, cnt.get(), off.get(), runs + 1, s));
   t = tb;
-  RMX_HIP(hipcub::DeviceSegmentedReduce::Sum(tmp.p, t, lab_s.p, posr.p, runs, off.p, off.p + 1, s));
-  hipLaunchKernelGGL(neg_kernel, dim3((runs + 255) / 256), dim3(256), 0, s, runs, cnt.p, posr.p, negr.p);
+  RMX_HIP(hipcub::DeviceSegmentedReduce::Sum(tmp.get(), t, lab_s.get(), posr.get(), runs, off.get(), off.get() + 1, s));
+  hipLaunchKernelGGL(neg_kernel, dim3((runs + 255) / 256), dim3(256), 0, s, runs, cnt.get(), posr.get(), negr.get());
   RMX_HIP(hipGetLastError());
   // negatives before each run (64-bit running count)
-  hipLaunchKernelGGL(widen_kernel, dim3((runs + 255) / 256), dim3(256), 0, s, runs, negr.p, negr64.p);
+  hipLaunchKernelGGL(widen_kernel, dim3((runs + 255) / 256), dim3(256), 0, s, runs, negr.get(), negr64.get());
   RMX_HIP(hipGetLastError());
   t = tb;
-  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, negr64.p, negb.p, runs, s));
+  RMX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.get(), t, negr64.get(), negb.get(), runs, s));
   const int nb = (runs + 255) / 256;
-  if ((st = part.alloc(nb))) return st;
-  hipLaunchKernelGGL(auc_part_kernel, dim3(nb), dim3(256), 0, s, runs, posr.p, negr.p, negb.p, part.p);
+  if ((st = part.alloc(nb, who))) return st;
+  hipLaunchKernelGGL(auc_part_kernel, dim3(nb), dim3(256), 0, s, runs, posr.get(), negr.get(), negb.get(), part.get());
   RMX_HIP(hipGetLastError());
   std::vector<double> h(nb);
-  RMX_HIP(hipMemcpyAsync(h.data(), part.p, sizeof(double) * nb, hipMemcpyDeviceToHost, s));
+  RMX_HIP(hipMemcpyAsync(h.data(), part.get(), sizeof(double) * nb, hipMemcpyDeviceToHost, s));
   RMX_HIP(hipStreamSynchronize(s));
   // P from the last exclusive-scan entry + last run, via one more small copy
   long long nb_last = 0;
   int neg_last = 0;
-  RMX_HIP(hipMemcpyAsync(&nb_last, negb.p + (runs - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
-  RMX_HIP(hipMemcpyAsync(&neg_last, negr.p + (runs - 1), sizeof(int), hipMemcpyDeviceToHost, s));
+  RMX_HIP(hipMemcpyAsync(&nb_last, negb.get() + (runs - 1), sizeof(long long), hipMemcpyDeviceToHost, s));
+  RMX_HIP(hipMemcpyAsync(&neg_last, negr.get() + (runs - 1), sizeof(int), hipMemcpyDeviceToHost, s));
   RMX_HIP(hipStreamSynchronize(s));
   const double N = (double)(nb_last + neg_last), P = (double)n - N;
   double sum = 0.0;

@@ -122,53 +122,18 @@ DenseLayer make_layer(int K, int N, int64_t w_off, int64_t b_off) {
   return L;
 }
 
-int dev_alloc(float** p, size_t n) {
-  if (hipMalloc(p, sizeof(float) * (n ? n : 1)) != hipSuccess) {
-    set_error("out of device memory (" + std::to_string(n * 4) + " bytes)");
-    return RMX_E_NOMEM;
-  }
-  return RMX_OK;
-}
-
-int dev_alloc_bf16(bf16_t** p, int64_t n) {
-  if (hipMalloc(p, sizeof(bf16_t) * (n > 0 ? n : 1)) != hipSuccess) {
-    set_error("out of device memory (" + std::to_string(n * 2) + " bytes)");
-    return RMX_E_NOMEM;
-  }
-  return RMX_OK;
-}
-
-template <class T>
-void dev_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-// scratch buffers (workspace, L-A staging): allocated and recorded with their size / forgotten and freed
-int ws_alloc(rmx_model& m, float** p, size_t n) {
-  const int st = dev_alloc(p, n);
-  if (st == RMX_OK) scratch_note(m, *p, sizeof(float) * (n ? n : 1));
-  return st;
-}
-
-template <class T>
-void ws_free(rmx_model& m, T*& p) {
-  scratch_forget(m, p);
-  dev_free(p);
-}
-
 // W^T planes for the backward's dX on the split GEMM (single-block fp32 layers whose input width
 // pads to a multiple of 208 with at most one extra 16-wide tile, e.g. 400 -> 416, 624; the dX buffer's
 // row stride must also hold NTpad, checked at launch: dx_s3_usable)
 int alloc_wt(DenseLayer& L) {
-  dev_free(L.WT);
-  dev_free(L.WT3);
+  L.WT.reset();
+  L.WT3.reset();
   L.KTpad = L.NTpad = 0;
   if (L.K1 >= 0 || L.N1 >= 0 || round_up(L.K, 208) - round_up(L.K, kChunk) > kChunk) return RMX_OK;
   L.KTpad = round_up(L.N, kChunk);
   L.NTpad = round_up(L.K, 208);
-  int st = dev_alloc(&L.WT, (size_t)L.KTpad * L.NTpad);
-  if (!st) st = dev_alloc_bf16(&L.WT3, split3_elems(L.KTpad / kChunk, L.NTpad));
+  int st = L.WT.alloc((size_t)L.KTpad * L.NTpad, "model");
+  if (!st) st = L.WT3.alloc(split3_elems(L.KTpad / kChunk, L.NTpad), "model");
   return st;
 }
 
@@ -182,19 +147,6 @@ int xbuf_ld_max(const rmx_model& m) { return round_up(m.layers[0].Kpad, m.precis
 int xbuf_ld(const rmx_model& m) { return tuning_get("x_line_pad", 1) ? xbuf_ld_max(m) : m.layers[0].Kpad; }
 
 }  // namespace
-
-void scratch_note(rmx_model& m, void* p, size_t bytes) {
-  if (p) m.scratch.push_back({p, bytes});
-}
-
-void scratch_forget(rmx_model& m, void* p) {
-  if (!p) return;
-  for (size_t i = 0; i < m.scratch.size(); ++i)
-    if (m.scratch[i].ptr == p) {
-      m.scratch.erase(m.scratch.begin() + i);
-      return;
-    }
-}
 
 int model_build(rmx_model& m) {
   const int t = m.type;
@@ -285,7 +237,7 @@ int model_build(rmx_model& m) {
         off += (int64_t)m.F * hp * h + h;
         hp = h;
         sum += h;
-        m.cin_layers.push_back(c);
+        m.cin_layers.push_back(std::move(c));
       }
       m.wo_cin_off = off;
       int base = 0;
@@ -314,7 +266,7 @@ int model_build(rmx_model& m) {
           L.nx = m.cross_depth;
           L.w_off_x = m.cross_w_off;
         }
-        m.layers.push_back(L);
+        m.layers.push_back(std::move(L));
         off += (int64_t)prev * d + d;
         prev = d;
       }
@@ -330,7 +282,7 @@ int model_build(rmx_model& m) {
       L0.K1 = D;
       L0.w_off2 = (int64_t)D * D1;
       L0.bias_mode = 2;
-      m.layers.push_back(L0);
+      m.layers.push_back(std::move(L0));
       off = (int64_t)D * D1 + (int64_t)P * D1 + 1;
       int prev = D1;
       for (size_t i = 1; i < m.fc.size(); ++i) {
@@ -355,41 +307,38 @@ int model_build(rmx_model& m) {
   // device parameter buffers
   RMX_HIP(hipSetDevice(m.ctx->device));
   int st = RMX_OK;
-  if (m.mats_len > 0 && (st = dev_alloc(&m.mats_dev, m.mats_len))) return st;
+  if (m.mats_len > 0 && (st = m.mats_dev.alloc(m.mats_len, "model"))) return st;
   for (auto& L : m.layers) {
-    if ((st = dev_alloc(&L.W, (size_t)L.Kpad * L.Npad))) return st;
-    if ((st = dev_alloc_bf16(&L.W3, split3_elems(L.Kpad / kChunk, L.Npad)))) return st;
-    if ((st = dev_alloc(&L.b, L.Npad))) return st;
+    if ((st = L.W.alloc((size_t)L.Kpad * L.Npad, "model"))) return st;
+    if ((st = L.W3.alloc(split3_elems(L.Kpad / kChunk, L.Npad), "model"))) return st;
+    if ((st = L.b.alloc(L.Npad, "model"))) return st;
     if ((st = alloc_wt(L))) return st;
   }
   if (!m.layers.empty()) {
-    if ((st = dev_alloc(&m.wo, m.layers.back().Npad))) return st;
+    if ((st = m.wo.alloc(m.layers.back().Npad, "model"))) return st;
   }
   for (auto& c : m.cin_layers) {
-    if ((st = dev_alloc(&c.W, (size_t)c.Hp_pad * m.F * c.Npad))) return st;
-    if ((st = dev_alloc_bf16(&c.W3, split3_elems(c.Hp_pad / kChunk * m.F, c.Npad)))) return st;
+    if ((st = c.W.alloc((size_t)c.Hp_pad * m.F * c.Npad, "model"))) return st;
+    if ((st = c.W3.alloc(split3_elems(c.Hp_pad / kChunk * m.F, c.Npad), "model"))) return st;
     {  // the split kernel's K order (k_gemm.hip cin_chunk_map): at most Hp_pad / 16 * F chunks
       c.tri = &c == &m.cin_layers.front() ? 1 : 0;
       const std::vector<int> map = cin_chunk_map(m.F, c.Hp, c.tri != 0);
       c.ncm = (int)map.size();
-      if (hipMalloc(&c.cmap, sizeof(int) * std::max<size_t>(map.size(), 1)) != hipSuccess) {
-        set_error("out of device memory (CIN chunk map)");
-        return RMX_E_NOMEM;
-      }
+      if ((st = c.cmap.alloc(map.size(), "model (CIN chunk map)"))) return st;
       RMX_HIP(hipMemcpy(c.cmap, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
-      if ((st = dev_alloc(&c.Wm, (size_t)c.ncm * c.Npad * 16))) return st;
+      if ((st = c.Wm.alloc((size_t)c.ncm * c.Npad * 16, "model"))) return st;
     }
     c.KTpad = round_up(c.H, kChunk);
     c.NTpad = round_up(m.F * c.Hp, 208);
-    if ((st = dev_alloc(&c.WT, (size_t)c.KTpad * c.NTpad))) return st;
-    if ((st = dev_alloc_bf16(&c.WT3, split3_elems(c.KTpad / kChunk, c.NTpad)))) return st;
-    if ((st = dev_alloc(&c.b, c.Npad))) return st;
-    if ((st = dev_alloc(&c.wo, c.Npad))) return st;
+    if ((st = c.WT.alloc((size_t)c.KTpad * c.NTpad, "model"))) return st;
+    if ((st = c.WT3.alloc(split3_elems(c.KTpad / kChunk, c.NTpad), "model"))) return st;
+    if ((st = c.b.alloc(c.Npad, "model"))) return st;
+    if ((st = c.wo.alloc(c.Npad, "model"))) return st;
   }
   if (t == RMX_MODEL_DCN) {
-    if ((st = dev_alloc(&m.cross_w, (size_t)m.cross_depth * D))) return st;
-    if ((st = dev_alloc(&m.cross_b, m.cross_depth))) return st;
-    if ((st = dev_alloc(&m.wo_x, D))) return st;
+    if ((st = m.cross_w.alloc((size_t)m.cross_depth * D, "model"))) return st;
+    if ((st = m.cross_b.alloc(m.cross_depth, "model"))) return st;
+    if ((st = m.wo_x.alloc(D, "model"))) return st;
   }
   if (t == RMX_MODEL_PNN) {
     // pairs (i < j) lexicographic: ProductEncoder.calcIndices (ProductEncoder.scala:110-120)
@@ -399,10 +348,7 @@ int model_build(rmx_model& m) {
         pr.push_back(i);
         pr.push_back(j);
       }
-    if (hipMalloc(&m.pairs, sizeof(int32_t) * pr.size()) != hipSuccess) {
-      set_error("out of device memory");
-      return RMX_E_NOMEM;
-    }
+    if ((st = m.pairs.alloc(pr.size(), "model"))) return st;
     RMX_HIP(hipMemcpy(m.pairs, pr.data(), sizeof(int32_t) * pr.size(), hipMemcpyHostToDevice));
   }
   return RMX_OK;
@@ -447,57 +393,15 @@ void model_init_mats(const rmx_model& m, uint64_t seed, float* mats) {
   }
 }
 
+// What is not memory: the buffers go with their owners' destructors at the caller's delete, after the
+// synchronisation here.
 void model_release(rmx_model& m) {
   train_release(m);
-  for (void* p : {(void*)m.la_grad.gw, (void*)m.la_grad.ge, (void*)m.la_grad.gm, (void*)m.la_grad.gb,
-                  (void*)m.la_grad.tg, (void*)m.la_grad.idx})
-    if (p) (void)hipFree(p);
-  m.la_grad = rmx_model::LaGrad{};
   if (!m.ctx) return;
   (void)hipSetDevice(m.ctx->device);
   (void)hipDeviceSynchronize();  // the last calls may have run on any stream
   if (m.ws_fence) (void)hipEventDestroy(m.ws_fence);
   m.ws_fence = nullptr;
-  dev_free(m.mats_dev);
-  for (auto& L : m.layers) {
-    dev_free(L.W);
-    dev_free(L.W16);
-    dev_free(L.W3);
-    dev_free(L.WT);
-    dev_free(L.WT3);
-    dev_free(L.b);
-  }
-  dev_free(m.wo);
-  for (auto& c : m.cin_layers) {
-    dev_free(c.W);
-    dev_free(c.W3);
-    dev_free(c.Wm);
-    dev_free(c.cmap);
-    dev_free(c.WT);
-    dev_free(c.WT3);
-    dev_free(c.b);
-    dev_free(c.wo);
-  }
-  dev_free(m.cross_w);
-  dev_free(m.cross_b);
-  dev_free(m.wo_x);
-  dev_free(m.pairs);
-  ws_free(m, m.h[0]);
-  ws_free(m, m.h[1]);
-  ws_free(m, m.y12);
-  ws_free(m, m.pre2);
-  ws_free(m, m.xcol);
-  ws_free(m, m.xbuf);
-  ws_free(m, m.ubuf[0]);
-  ws_free(m, m.ubuf[1]);
-  ws_free(m, m.rowdot);
-  ws_free(m, m.opart);
-  ws_free(m, m.la_E);
-  ws_free(m, m.la_w);
-  ws_free(m, m.la_E16);
-  ws_free(m, m.la_w16);
-  dev_free(m.la_rowptr);
-  ws_free(m, m.la_out);
   for (auto& p : m.pending) {
     (void)hipEventDestroy(p.a);
     (void)hipEventDestroy(p.b);
@@ -522,20 +426,18 @@ int model_set_precision(rmx_model& m, int dtype) {
   RMX_HIP(hipSetDevice(m.ctx->device));
   RMX_HIP(hipStreamSynchronize(m.ctx->stream));
   for (auto& L : m.layers) {
-    dev_free(L.W);
-    dev_free(L.W16);
-    dev_free(L.W3);
-    dev_free(L.WT);
-    dev_free(L.WT3);
+    L.W.reset();
+    L.W16.reset();
+    L.W3.reset();
+    L.WT.reset();
+    L.WT3.reset();
     L.Kpad = round_up(L.K, dtype == kBF16 ? 32 : kChunk);
     if (dtype == kBF16) {
-      if (hipMalloc(&L.W16, sizeof(bf16_t) * (size_t)L.Kpad * L.Npad) != hipSuccess) {
-        set_error("out of device memory");
-        return RMX_E_NOMEM;
-      }
+      const int st = L.W16.alloc((size_t)L.Kpad * L.Npad, "model");
+      if (st) return st;
     } else {
-      int st = dev_alloc(&L.W, (size_t)L.Kpad * L.Npad);
-      if (!st) st = dev_alloc_bf16(&L.W3, split3_elems(L.Kpad / kChunk, L.Npad));
+      int st = L.W.alloc((size_t)L.Kpad * L.Npad, "model");
+      if (!st) st = L.W3.alloc(split3_elems(L.Kpad / kChunk, L.Npad), "model");
       if (!st) st = alloc_wt(L);
       if (st) return st;
     }
@@ -544,9 +446,9 @@ int model_set_precision(rmx_model& m, int dtype) {
   m.params_ready = false;
   // workspaces depend on Kpad (PNN [x | ip] rows): rebuild on the next call
   RMX_HIP(hipStreamSynchronize(m.ctx->stream));
-  ws_free(m, m.xbuf);
+  m.xbuf.reset();
   m.xbuf_B = 0;
-  m.ws_B = 0;
+  m.ws.B = 0;
   return RMX_OK;
 }
 
@@ -627,48 +529,39 @@ namespace {
 int ensure_xbuf(rmx_model& m, int B) {
   if (B <= m.xbuf_B && m.xbuf) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());  // earlier calls on any stream may still read the old buffer
-  ws_free(m, m.xbuf);
   m.xbuf_B = 0;
-  const int st = ws_alloc(m, &m.xbuf, (size_t)B * xbuf_ld_max(m));
+  const int st = m.xbuf.alloc(m.scratch, (size_t)B * xbuf_ld_max(m), "workspace");
   if (st == RMX_OK) m.xbuf_B = B;
   return st;
 }
 
 int ensure_ws(rmx_model& m, int B) {
-  if (B <= m.ws_B) return RMX_OK;
+  if (B <= m.ws.B) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());  // earlier calls on any stream may still read the old buffers
-  ws_free(m, m.h[0]);
-  ws_free(m, m.h[1]);
-  ws_free(m, m.y12);
-  ws_free(m, m.pre2);
-  ws_free(m, m.xcol);
-  ws_free(m, m.ubuf[0]);
-  ws_free(m, m.ubuf[1]);
-  ws_free(m, m.rowdot);
-  ws_free(m, m.opart);
+  m.ws = rmx_model::Workspace{};
   int st;
   int maxN = 16;
   for (auto& L : m.layers) maxN = std::max(maxN, L.Npad);
   if (!m.layers.empty()) {
-    if ((st = ws_alloc(m, &m.h[0], (size_t)B * maxN))) return st;
-    if ((st = ws_alloc(m, &m.h[1], (size_t)B * maxN))) return st;
+    if ((st = m.ws.h[0].alloc(m.scratch, (size_t)B * maxN, "workspace"))) return st;
+    if ((st = m.ws.h[1].alloc(m.scratch, (size_t)B * maxN, "workspace"))) return st;
     // partial logits of an output layer run in column slices (k_gemm_s3.hip)
     // (up to Npad / 16 slices: 208-column slices, or the 32-column blocks of small batches, s3_cols)
-    if ((st = ws_alloc(m, &m.opart, (size_t)B * (m.layers.back().Npad / 16 + 1)))) return st;
+    if ((st = m.ws.opart.alloc(m.scratch, (size_t)B * (m.layers.back().Npad / 16 + 1), "workspace"))) return st;
   }
-  if ((st = ws_alloc(m, &m.y12, B))) return st;
-  if ((st = ws_alloc(m, &m.pre2, B))) return st;
-  if (m.dcn_fused && (st = ws_alloc(m, &m.xcol, (size_t)B * (m.cross_depth + 1)))) return st;
+  if ((st = m.ws.y12.alloc(m.scratch, B, "workspace"))) return st;
+  if ((st = m.ws.pre2.alloc(m.scratch, B, "workspace"))) return st;
+  if (m.dcn_fused && (st = m.ws.xcol.alloc(m.scratch, (size_t)B * (m.cross_depth + 1), "workspace"))) return st;
   if ((m.type == RMX_MODEL_PNN || (m.type != RMX_MODEL_LR && needs_gather_x(m))) && (st = ensure_xbuf(m, B)))
     return st;
   if (!m.cin_layers.empty()) {
     int maxH = 16;
     for (auto& c : m.cin_layers) maxH = std::max(maxH, c.Npad);
-    if ((st = ws_alloc(m, &m.ubuf[0], (size_t)B * m.k * maxH))) return st;
-    if ((st = ws_alloc(m, &m.ubuf[1], (size_t)B * m.k * maxH))) return st;
-    if ((st = ws_alloc(m, &m.rowdot, (size_t)B * m.k))) return st;
+    if ((st = m.ws.ubuf[0].alloc(m.scratch, (size_t)B * m.k * maxH, "workspace"))) return st;
+    if ((st = m.ws.ubuf[1].alloc(m.scratch, (size_t)B * m.k * maxH, "workspace"))) return st;
+    if ((st = m.ws.rowdot.alloc(m.scratch, (size_t)B * m.k, "workspace"))) return st;
   }
-  m.ws_B = B;
+  m.ws.B = B;
   return RMX_OK;
 }
 
@@ -736,7 +629,7 @@ void table_inputs(const rmx_table& t, const rmx_model& m, FwdInputs& in) {
   in.dtype = t.dtype;
   if (t.line && model_reads_lines(m)) {
     in.table = t.line;
-    in.wtab = t.dtype == kBF16 ? (const void*)(reinterpret_cast<const bf16_t*>(t.line) + 16) : (const void*)(t.line + 16);
+    in.wtab = t.dtype == kBF16 ? (const void*)(reinterpret_cast<const bf16_t*>(t.line.get()) + 16) : (const void*)(t.line + 16);
     in.ld = in.wld = 32;
   } else {
     in.table = t.emb;
@@ -784,7 +677,7 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
     if (in.ids && (st = ensure_xbuf(m, B))) return st;
     {
       StageTimer t(m, s, "encoder_fm_x");
-      if ((st = launch_encoder(s, 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr, nullptr, in.ld,
+      if ((st = launch_encoder(s, 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.ws.y12, nullptr, nullptr, in.ld,
                                in.wld, in.ids ? m.xbuf : nullptr)))
         return st;
     }
@@ -792,17 +685,17 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
     oa.wo = m.wo;
     oa.bo = m.bo;
     oa.has_bo = m.has_bo ? 1 : 0;
-    oa.pre = m.y12;
+    oa.pre = m.ws.y12;
     oa.beta = in.beta;
     oa.out = in.out;
-    oa.part = m.opart;
+    oa.part = m.ws.opart;
     const float* A = in.ids ? m.xbuf : (const float*)in.table;
     int lda = F * k;
     static const char* lnames[] = {"tower_layer1", "tower_layer2", "tower_layer3", "tower_layer4+"};
     for (size_t i = 0; i < m.layers.size(); ++i) {
       const bool last = i + 1 == m.layers.size();
       const DenseLayer& L = m.layers[i];
-      float* C = m.h[i & 1];
+      float* C = m.ws.h[i & 1];
       StageTimer t(m, s, lnames[std::min<size_t>(i, 3)]);
       if ((st = launch_tower_layer(s, L, B, A, lda, nullptr, C, L.Npad, last ? Epi::kOutput : Epi::kReluStore,
                                    last ? &oa : nullptr, nullptr, nullptr, true)))
@@ -875,23 +768,23 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
                       (fm_y1 == 0 || (fm_y1 == 2 && !tower_wring(m.layers[0], B, &ga)));
   if (fm_add) {
     StageTimer t(m, s, "first_order");
-    if ((st = launch_encoder(s, 0, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr, nullptr, in.ld,
+    if ((st = launch_encoder(s, 0, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.ws.y12, nullptr, nullptr, in.ld,
                              in.wld)))
       return st;
   }
   if (fm_fused || head_s3) {
-    pre = m.y12;
+    pre = m.ws.y12;
   } else if (m.type == RMX_MODEL_DEEPFM) {
     StageTimer t(m, s, "encoder_fm");
-    st = launch_encoder(s, in.y1 ? 3 : 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr, nullptr, in.ld,
+    st = launch_encoder(s, in.y1 ? 3 : 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.ws.y12, nullptr, nullptr, in.ld,
                         in.wld);
-    pre = m.y12;
+    pre = m.ws.y12;
   } else if (m.type != RMX_MODEL_DNN) {
     if (!in.y1 && !tail_fo) {
       StageTimer t(m, s, "first_order");
-      st = launch_encoder(s, 0, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr, nullptr, in.ld, in.wld);
+      st = launch_encoder(s, 0, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.ws.y12, nullptr, nullptr, in.ld, in.wld);
     }
-    pre = tail_fo ? nullptr : m.y12;  // (the L-A irregular path already wrote y1 here)
+    pre = tail_fo ? nullptr : m.ws.y12;  // (the L-A irregular path already wrote y1 here)
   }
   if (st) return st;
 
@@ -903,7 +796,7 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
   oa.pre = pre;
   oa.beta = in.beta;
   oa.out = in.out;
-  oa.part = m.opart;
+  oa.part = m.ws.opart;
   const float* A = nullptr;
   int lda = 0;
 
@@ -912,22 +805,22 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
     for (size_t l = 0; l < m.cin_layers.size(); ++l) {
       StageTimer t(m, s, l == 0 ? "cin_layer1" : (l == 1 ? "cin_layer2" : "cin_layer3+"));
       const bool last = l + 1 == m.cin_layers.size();
-      float* uout = last ? nullptr : m.ubuf[l & 1];
+      float* uout = last ? nullptr : m.ws.ubuf[l & 1];
       if ((st = launch_cin_layer(s, m.cin_layers[l], l == 0, last, B, F, k, in.ids, (const float*)in.table, uprev, uout,
-                                 m.rowdot)))
+                                 m.ws.rowdot)))
         return st;
       uprev = uout;
     }
-    oa.rowsum = m.rowdot;
+    oa.rowsum = m.ws.rowdot;
     oa.rowsum_k = k;
   } else if (m.type == RMX_MODEL_DCN) {
     if (!m.dcn_fused) {
       StageTimer t(m, s, "cross");
       if ((st = launch_cross(s, B, F, k, m.cross_depth, in.ids, in.table, in.dtype, m.cross_w, m.cross_b, m.wo_x,
-                             m.pre2)))
+                             m.ws.pre2)))
         return st;
     }
-    oa.pre2 = m.pre2;
+    oa.pre2 = m.ws.pre2;
   } else if (m.type == RMX_MODEL_PNN) {
     StageTimer t(m, s, "product");
     if ((st = launch_product(s, B, F, k, in.ids, in.table, in.dtype, m.pairs, F * (F - 1) / 2, m.xbuf, m.precision,
@@ -963,23 +856,23 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
       StageTimer t(m, s, "tower_tail");
       return launch_tower_tail_s3(s, L, m.layers[i + 1], B, A, lda, oa);
     }
-    float* C = m.h[i & 1];
+    float* C = m.ws.h[i & 1];
     StageTimer t(m, s, names[std::min<size_t>(i, 3)]);
     if (i == 0 && head_s3) {
       if ((st = launch_tower_head_s3(s, L, B, F, in.ids, (const float*)in.table, in.ld, (const float*)in.wtab, in.wld, C,
-                                     L.Npad, m.y12, 1)))
+                                     L.Npad, m.ws.y12, 1)))
         return st;
       A = C;
       lda = L.Npad;
       continue;
     }
-    XColArgs xc{m.xcol, L.N1, m.cross_depth + 1};
-    FmArgs fm{in.wtab, in.dtype == kBF16 ? 1 : 0, deepfm ? 1 : 0, fm_add ? 1 : 0, m.y12, in.wld};
+    XColArgs xc{m.ws.xcol, L.N1, m.cross_depth + 1};
+    FmArgs fm{in.wtab, in.dtype == kBF16 ? 1 : 0, deepfm ? 1 : 0, fm_add ? 1 : 0, m.ws.y12, in.wld};
     st = launch_tower_layer(s, L, B, A, lda, (i == 0 && gather_first) ? &ga : nullptr, C, L.Npad,
                             last ? Epi::kOutput : Epi::kReluStore, last ? &oa : nullptr,
                             (i == 0 && m.dcn_fused) ? &xc : nullptr, (i == 0 && fm_fused) ? &fm : nullptr);
     if (st) return st;
-    if (i == 0 && m.dcn_fused && (st = launch_cross_finish(s, B, m.cross_depth, m.xcol, m.cross_scalars, m.pre2)))
+    if (i == 0 && m.dcn_fused && (st = launch_cross_finish(s, B, m.cross_depth, m.ws.xcol, m.cross_scalars, m.ws.pre2)))
       return st;
     A = C;
     lda = L.Npad;
@@ -996,21 +889,16 @@ int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, boo
   int st;
   if (nnz > m.la_nnz) {
     RMX_HIP(hipDeviceSynchronize());
-    ws_free(m, m.la_E);
-    ws_free(m, m.la_w);
-    if (m.type != RMX_MODEL_LR && (st = ws_alloc(m, &m.la_E, (size_t)nnz * m.k))) return st;
-    if ((st = ws_alloc(m, &m.la_w, nnz))) return st;
+    m.la_nnz = 0;
+    if (m.type != RMX_MODEL_LR && (st = m.la_E.alloc(m.scratch, (size_t)nnz * m.k, "L-A staging"))) return st;
+    if ((st = m.la_w.alloc(m.scratch, nnz, "L-A staging"))) return st;
     m.la_nnz = nnz;
   }
   if (B > m.la_B) {
     RMX_HIP(hipDeviceSynchronize());
-    ws_free(m, m.la_out);
-    dev_free(m.la_rowptr);  // (row pointers: never in the scratch list, a leftover there would be an address)
-    if ((st = ws_alloc(m, &m.la_out, B))) return st;
-    if (hipMalloc(&m.la_rowptr, sizeof(int64_t) * (B + 1)) != hipSuccess) {
-      set_error("out of device memory");
-      return RMX_E_NOMEM;
-    }
+    m.la_B = 0;
+    if ((st = m.la_out.alloc(m.scratch, B, "L-A staging"))) return st;
+    if ((st = m.la_rowptr.alloc((size_t)B + 1, "L-A staging"))) return st;
     m.la_B = B;
   }
   if ((st = ensure_ws(m, B))) return st;
@@ -1049,16 +937,10 @@ int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, boo
     // (la_w in place too, so the Scatter first order below sums the rounded weights)
     if (nnz * std::max(m.k, 1) > m.la16_cap) {
       RMX_HIP(hipDeviceSynchronize());
-      ws_free(m, m.la_E16);
-      ws_free(m, m.la_w16);
       m.la16_cap = 0;
-      if (hipMalloc(&m.la_E16, sizeof(bf16_t) * nnz * std::max(m.k, 1)) != hipSuccess ||
-          hipMalloc(&m.la_w16, sizeof(bf16_t) * nnz) != hipSuccess) {
-        set_error("out of device memory");
-        return RMX_E_NOMEM;
-      }
-      scratch_note(m, m.la_E16, sizeof(bf16_t) * nnz * std::max(m.k, 1));
-      scratch_note(m, m.la_w16, sizeof(bf16_t) * nnz);
+      if ((st = m.la_E16.alloc(m.scratch, (size_t)nnz * std::max(m.k, 1), "L-A staging")) ||
+          (st = m.la_w16.alloc(m.scratch, (size_t)nnz, "L-A staging")))
+        return st;
       m.la16_cap = nnz * std::max(m.k, 1);
     }
     if (m.type != RMX_MODEL_LR && (st = launch_convert_bf16(s, m.la_E, nnz * m.k, m.la_E16))) return st;
@@ -1074,7 +956,7 @@ int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, boo
       for (int b = 0; b < B; ++b) m.h_rowptr[b + 1] += m.h_rowptr[b];
     }
     RMX_HIP(hipMemcpyAsync(m.la_rowptr, m.h_rowptr.data(), sizeof(int64_t) * (B + 1), hipMemcpyHostToDevice, s));
-    if ((st = launch_first_order_csr(s, B, m.la_rowptr, m.la_w, m.y12))) return st;
+    if ((st = launch_first_order_csr(s, B, m.la_rowptr, m.la_w, m.ws.y12))) return st;
   }
   FwdInputs in;
   in.B = B;
@@ -1086,7 +968,7 @@ int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, boo
     in.wtab = m.la_w16;
     in.dtype = kBF16;
   }
-  in.y1 = csr ? m.y12 : nullptr;
+  in.y1 = csr ? m.ws.y12 : nullptr;
   in.beta = bias;
   in.out = m.la_out;
   *pin = in;

@@ -454,20 +454,8 @@ __global__ void host_vals_kernel(HostValArgs a, float* __restrict__ hv) {
   if (t == 3 + kMaxFusedCross) hv[kOptimHostVals - 1] = a.loss ? a.loss[0] : 0.f;
 }
 
-template <class T>
-int dalloc(T** p, size_t n) {
-  if (hipMalloc(p, sizeof(T) * std::max<size_t>(n, 4)) != hipSuccess) {
-    *p = nullptr;
-    set_error("rmx_optim: out of device memory");
-    return RMX_E_NOMEM;
-  }
-  return RMX_OK;
-}
-template <class T>
-void dfree(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
+// every buffer of the optimiser holds at least 4 elements
+constexpr size_t kMinElems = 4;
 
 int id_bits(int64_t V) {  // bits of the largest key, V itself (the key of an id outside the table)
   int b = 1;
@@ -478,25 +466,17 @@ int id_bits(int64_t V) {  // bits of the largest key, V itself (the key of an id
 int ensure_scratch(rmx_optim& o, int64_t nnz) {
   if (nnz <= o.cap_nnz) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
-  for (int i = 0; i < 2; ++i) {
-    dfree(o.keys[i]);
-    dfree(o.vals[i]);
-  }
-  dfree(o.hist);
-  dfree(o.bsum);
-  dfree(o.part);
-  dfree(o.long_head);
   o.cap_nnz = 0;
   const size_t tiles = (size_t)((nnz + kRsTile - 1) / kRsTile), windows = (size_t)(nnz / kChunkRows + 1);
   int st = RMX_OK;
   for (int i = 0; i < 2 && !st; ++i) {
-    st = dalloc(&o.keys[i], (size_t)nnz);
-    if (!st) st = dalloc(&o.vals[i], (size_t)nnz);
+    st = o.keys[i].alloc((size_t)nnz, "rmx_optim", kMinElems);
+    if (!st) st = o.vals[i].alloc((size_t)nnz, "rmx_optim", kMinElems);
   }
-  if (!st) st = dalloc(&o.hist, tiles * kRsBins);
-  if (!st) st = dalloc(&o.bsum, tiles * kRsBins / kScanBlock + 1);
-  if (!st) st = dalloc(&o.part, 2 * windows * ((size_t)o.t->k + 1));
-  if (!st) st = dalloc(&o.long_head, windows);
+  if (!st) st = o.hist.alloc(tiles * kRsBins, "rmx_optim", kMinElems);
+  if (!st) st = o.bsum.alloc(tiles * kRsBins / kScanBlock + 1, "rmx_optim", kMinElems);
+  if (!st) st = o.part.alloc(2 * windows * ((size_t)o.t->k + 1), "rmx_optim", kMinElems);
+  if (!st) st = o.long_head.alloc(windows, "rmx_optim", kMinElems);
   if (st) return st;
   o.cap_nnz = nnz;
   return RMX_OK;
@@ -541,68 +521,48 @@ int optim_alloc(rmx_optim& o) {
   int st = RMX_OK;
   for (int i = 0; i < o.nslots && !st; ++i) {
     if (o.upd_w) {
-      if ((st = dalloc(&o.w_s[i], (size_t)t.V))) break;
+      if ((st = o.w_s[i].alloc((size_t)t.V, "rmx_optim", kMinElems))) break;
       RMX_HIP(hipMemsetAsync(o.w_s[i], 0, sizeof(float) * t.V, m.ctx->stream));
     }
     if (o.upd_e && t.k > 0) {
-      if ((st = dalloc(&o.e_s[i], (size_t)t.V * t.k))) break;
+      if ((st = o.e_s[i].alloc((size_t)t.V * t.k, "rmx_optim", kMinElems))) break;
       RMX_HIP(hipMemsetAsync(o.e_s[i], 0, sizeof(float) * t.V * t.k, m.ctx->stream));
     }
     if (m.mats_len > 0) {
-      if ((st = dalloc(&o.m_s[i], (size_t)m.mats_len))) break;
+      if ((st = o.m_s[i].alloc((size_t)m.mats_len, "rmx_optim", kMinElems))) break;
       RMX_HIP(hipMemsetAsync(o.m_s[i], 0, sizeof(float) * m.mats_len, m.ctx->stream));
     }
   }
-  if (!st) st = dalloc(&o.b_s, 2);
-  if (!st) st = dalloc(&o.hv, kOptimHostVals);
-  if (st) {
-    optim_release(o);
-    return st;
-  }
+  if (!st) st = o.b_s.alloc(2, "rmx_optim", kMinElems);
+  if (!st) st = o.hv.alloc(kOptimHostVals, "rmx_optim", kMinElems);
+  if (st) return st;
   RMX_HIP(hipMemsetAsync(o.b_s, 0, sizeof(float) * 2, m.ctx->stream));
   RMX_HIP(hipStreamSynchronize(m.ctx->stream));
   return RMX_OK;
 }
 
+// The buffers go with the object at the caller's delete, after the synchronisation here.
 void optim_release(rmx_optim& o) {
   if (o.m && o.m->ctx) {
     (void)hipSetDevice(o.m->ctx->device);
     (void)hipDeviceSynchronize();
   }
-  for (int i = 0; i < 2; ++i) {
-    dfree(o.w_s[i]);
-    dfree(o.e_s[i]);
-    dfree(o.m_s[i]);
-    dfree(o.keys[i]);
-    dfree(o.vals[i]);
-  }
-  dfree(o.b_s);
-  dfree(o.hv);
-  dfree(o.hist);
-  dfree(o.bsum);
-  dfree(o.part);
-  dfree(o.long_head);
-  dfree(o.g_b);
-  dfree(o.g_w);
-  dfree(o.g_e);
-  dfree(o.g_m);
-  o.cap_nnz = o.g_nnz = 0;
 }
 
 int optim_ensure_grads(rmx_optim& o, int64_t nnz) {
   int st = RMX_OK;
   if (!o.g_b) {
-    st = dalloc(&o.g_b, 2);
-    if (!st && o.m->mats_len > 0) st = dalloc(&o.g_m, (size_t)o.m->mats_len);
+    st = o.g_b.alloc(2, "rmx_optim", kMinElems);
+    if (!st && o.m->mats_len > 0) st = o.g_m.alloc((size_t)o.m->mats_len, "rmx_optim", kMinElems);
     if (st) return st;
   }
   if (nnz <= o.g_nnz) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
-  dfree(o.g_w);
-  dfree(o.g_e);
+  o.g_w.reset();
+  o.g_e.reset();
   o.g_nnz = 0;
-  if (o.upd_w) st = dalloc(&o.g_w, (size_t)nnz);
-  if (!st && o.upd_e) st = dalloc(&o.g_e, (size_t)nnz * std::max(o.t->k, 1));
+  if (o.upd_w) st = o.g_w.alloc((size_t)nnz, "rmx_optim", kMinElems);
+  if (!st && o.upd_e) st = o.g_e.alloc((size_t)nnz * std::max(o.t->k, 1), "rmx_optim", kMinElems);
   if (st) return st;
   o.g_nnz = nnz;
   return RMX_OK;
@@ -653,8 +613,8 @@ int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, cons
     a.k = t.k;
     a.gw = g_w;
     a.ge = g_emb;
-    a.w = (float*)t.w;
-    a.emb = (float*)t.emb;
+    a.w = (float*)t.w.get();
+    a.emb = (float*)t.emb.get();
     a.line = t.line;
     a.ws1 = o.w_s[0];
     a.ws2 = o.w_s[1];

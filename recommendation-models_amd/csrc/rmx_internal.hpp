@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/rmx.h"
+#include "dev_buf.hpp"
 
 namespace rmx {
 
@@ -45,7 +46,9 @@ int tuning_get(const char* key, int def);  // rmx_set_tuning knobs (capi.hip)
 // A BigDL Linear(in = K, out = N) packed for the fp32 MFMA GEMM:
 //   W chunked as [Kpad/16][Npad][16] (each 16-wide K chunk of all N rows contiguous),
 //   zero padded in K and N; bias [Npad] zero padded.
-struct DenseLayer {
+// LayerPlan: where the layer's values sit in mats (what the pack kernels take by value); DenseLayer adds the
+// device planes it owns, and is move-only.
+struct LayerPlan {
   int K = 0, N = 0, Kpad = 0, Npad = 0;
   int64_t w_off = -1;   // offset of W (out x in row-major) in mats
   int64_t b_off = -1;   // offset of bias in mats, -1 = none
@@ -57,15 +60,17 @@ struct DenseLayer {
   // at w_off_o.  N = N1 + nx + 1 then.  -1: none.
   int N1 = -1, nx = 0;
   int64_t w_off_x = -1, w_off_o = -1;
-  float* W = nullptr;   // device, packed fp32 [Kpad/16][Npad][16]
-  bf16_t* W16 = nullptr;  // device, packed bf16 [Kpad/32][Npad][32] (bf16 models; W unused then)
-  bf16_t* W3 = nullptr;   // device, fp32 W split into 3 bf16 planes [ceil(Kpad/32)][3][Npad][32] (kPrecS3)
+};
+struct DenseLayer : LayerPlan {
+  DevBuf<float> W;      // device, packed fp32 [Kpad/16][Npad][16]
+  DevBuf<bf16_t> W16;     // device, packed bf16 [Kpad/32][Npad][32] (bf16 models; W unused then)
+  DevBuf<bf16_t> W3;      // device, fp32 W split into 3 bf16 planes [ceil(Kpad/32)][3][Npad][32] (kPrecS3)
   // W^T for the backward's dX = dPre W on the split GEMM (fp32 single-block layers, train.hip):
   // a Linear(in = N, out = K) packed like W (fp32 [KTpad/16][NTpad][16]) and split into WT3
   int KTpad = 0, NTpad = 0;
-  float* WT = nullptr;
-  bf16_t* WT3 = nullptr;
-  float* b = nullptr;   // device [Npad]
+  DevBuf<float> WT;
+  DevBuf<bf16_t> WT3;
+  DevBuf<float> b;      // device [Npad]
 };
 
 constexpr int kChunk = 16;  // K chunk of the GEMM (= one field row at k = 16)

@@ -19,8 +19,8 @@ struct rmx_table {
   int64_t V = 0;
   int k = 0;
   int dtype = 0;          // RMX_DTYPE_F32 / RMX_DTYPE_BF16 (elements of w and emb)
-  void* w = nullptr;      // [V]     first-order weights (Angel "weights" row 0)
-  void* emb = nullptr;    // [V][k]  embeddings, row-major (Angel "embedding" rows 0..k-1, transposed)
+  rmx::DevBuf<void> w;    // [V]     first-order weights (Angel "weights" row 0)
+  rmx::DevBuf<void> emb;  // [V][k]  embeddings, row-major (Angel "embedding" rows 0..k-1, transposed)
   // k = 16 tables with knob "table_lines" 1 (default 0): a [V][32] line copy (elements of dtype), row =
   // [emb 16 | w | pad 15] -- one 128-B memory line per id instead of a 64-B row line plus a separate weight
   // line (fp32), or one 64-B half line instead of a 32-B row line plus a weight line (bf16, round 5).
@@ -28,7 +28,7 @@ struct rmx_table {
   // device_ptrs); read by the models whose every table access takes a row stride
   // (rmx::model_reads_lines).  Measured ~1 % SLOWER for DeepFM layer 1 at V = 1M (0.1851 vs 0.1829 ms,
   // two A/B pairs on one box): the weight lines it saves hit the Infinity Cache, so it is off.
-  float* line = nullptr;   // (bf16 tables: bf16 elements)
+  rmx::DevBuf<float> line;  // (bf16 tables: bf16 elements, half as many floats)
 };
 
 namespace rmx {
@@ -63,26 +63,27 @@ struct CrossScalars {
 struct CinLayer {
   int Hp = 0, Hp_pad = 0, H = 0, Npad = 0;
   int64_t w_off = -1, b_off = -1, wo_off = -1;
-  float* W = nullptr;
-  float* b = nullptr;
-  float* wo = nullptr;  // [Npad] slice of the output Linear for this layer's pooled maps
-  bf16_t* W3 = nullptr;  // kPrecS3 planes of W (k_gemm_s3.hip), in the chunk-map K order when map_on
+  DevBuf<float> W;
+  DevBuf<float> b;
+  DevBuf<float> wo;     // [Npad] slice of the output Linear for this layer's pooled maps
+  DevBuf<bf16_t> W3;     // kPrecS3 planes of W (k_gemm_s3.hip), in the chunk-map K order when map_on
   // kPrecS3 K-chunk map (k_gemm.hpp cin_chunk): one entry f0 | hc << 16 | pair << 30 per 16-wide
   // chunk.  Layer 1 keeps only the h <= f half of its symmetric z = x0 (x) x0 (folded weights
   // C[f,h] + C[h,f]), and an h-chunk with <= 8 live maps carries two fields per chunk.
-  int* cmap = nullptr;
-  float* Wm = nullptr;  // fp32 [ncm][Npad][16] mapped weights (the split planes' source)
+  DevBuf<int> cmap;
+  DevBuf<float> Wm;     // fp32 [ncm][Npad][16] mapped weights (the split planes' source)
   int ncm = 0, tri = 0;
   int map_on = 0;       // W3 was packed in the mapped order (knob "cin_map" at set_mats)
   // backward dL/dz = gpre C_l on the split GEMM: C_l^T packed [KTpad/16][NTpad][16] (K = H, N = F Hp)
-  float* WT = nullptr;
-  bf16_t* WT3 = nullptr;
+  DevBuf<float> WT;
+  DevBuf<bf16_t> WT3;
   int KTpad = 0, NTpad = 0;
 };
 
 }  // namespace rmx
 
 struct rmx_model {
+  std::vector<rmx::Scratch> scratch;  // see "workspace" below; first, so that it is destroyed last
   rmx_ctx* ctx = nullptr;
   int type = 0;
   int64_t input_dim = 0;
@@ -93,50 +94,51 @@ struct rmx_model {
   int64_t mats_len = 0;
 
   // ---- device parameters (packed from mats) ----
-  float* mats_dev = nullptr;                // raw mats copy
+  rmx::DevBuf<float> mats_dev;              // raw mats copy
   std::vector<rmx::DenseLayer> layers;      // tower; the last one runs the output head
   int64_t wo_off = -1, bo_off = -1;         // output Linear weights / bias in mats
-  float* wo = nullptr;                      // device [Npad of last layer]
+  rmx::DevBuf<float> wo;                    // device [Npad of last layer]
   float bo = 0.f;
   bool has_bo = false;
   std::vector<rmx::CinLayer> cin_layers;    // xDeepFM
   int64_t wo_cin_off = -1;                  // start of the pooled-CIN slice of W_out
   int64_t cross_w_off = -1, cross_b_off = -1, wo_x_off = -1;  // DCN
-  float* cross_w = nullptr;                 // [L][D]
-  float* cross_b = nullptr;                 // [L]
-  float* wo_x = nullptr;                    // [D] slice of W_out for x_L
+  rmx::DevBuf<float> cross_w;               // [L][D]
+  rmx::DevBuf<float> cross_b;               // [L]
+  rmx::DevBuf<float> wo_x;                  // [D] slice of W_out for x_L
   bool dcn_fused = false;                   // cross dots fused into tower layer 1 (fcDims >= 2)
   rmx::CrossScalars cross_scalars{};
-  float* xcol = nullptr;                    // [B][L + 1] raw fused cross dots
-  int32_t* pairs = nullptr;                 // PNN (row, col) pairs [P][2]
+  rmx::DevBuf<int32_t> pairs;               // PNN (row, col) pairs [P][2]
   int precision = 0;                        // kF32 / kBF16 (rmx_model_set_precision)
   bool params_ready = false;
   float beta = 0.f;
   bool beta_set = false;
 
   // ---- workspace (grown on demand) ----
-  // every floating-point scratch buffer below, of the L-A staging and of TrainState, with its allocated size
-  // (rmx::scratch_note at the allocation, scratch_forget at the free): what rmx_debug_poison_workspace fills
-  struct Scratch { void* ptr; size_t bytes; };
-  std::vector<Scratch> scratch;
-  int ws_B = 0;
+  // every floating-point scratch buffer below, of the L-A staging and of TrainState, with its allocated size:
+  // the ScratchBuf members, listed here while they are allocated.  What rmx_debug_poison_workspace fills.
+  // (Declared in the struct's first lines, before every buffer: it outlives them all.)
+  struct Workspace {                  // the batch-sized inference buffers: one capacity, dropped together
+    int B = 0;
+    rmx::ScratchBuf<float> h[2];      // [B][Npad] tower activations
+    rmx::ScratchBuf<float> y12;       // [B] first order (+ FM)
+    rmx::ScratchBuf<float> pre2;      // [B] model-specific additive term (CIN / cross)
+    rmx::ScratchBuf<float> xcol;      // [B][L + 1] raw fused cross dots (DCN)
+    rmx::ScratchBuf<float> ubuf[2];   // [B*k][Npad] CIN maps
+    rmx::ScratchBuf<float> rowdot;    // [B*k] CIN per-row output partials
+    rmx::ScratchBuf<float> opart;     // [slices][B] partial logits of a column-sliced output layer
+  } ws;
   int xbuf_B = 0;                     // xbuf's own capacity (rows): grown where a path that needs it is chosen
-  float* h[2] = {nullptr, nullptr};   // [B][Npad] tower activations
-  float* y12 = nullptr;               // [B] first order (+ FM)
-  float* pre2 = nullptr;              // [B] model-specific additive term (CIN / cross)
-  float* xbuf = nullptr;              // [xbuf_B][Kpad0] materialised A (PNN [x | ip], generic k, DeepFM column-split x)
-  float* ubuf[2] = {nullptr, nullptr};  // [B*k][Npad] CIN maps
-  float* rowdot = nullptr;            // [B*k] CIN per-row output partials
-  float* opart = nullptr;             // [slices][B] partial logits of a column-sliced output layer
+  rmx::ScratchBuf<float> xbuf;        // [xbuf_B][Kpad0] materialised A (PNN [x | ip], generic k, DeepFM column-split x)
   // L-A staging
   int64_t la_nnz = 0;
   int la_B = 0;
-  float* la_E = nullptr;
-  float* la_w = nullptr;
-  int64_t* la_rowptr = nullptr;
-  float* la_out = nullptr;
-  rmx::bf16_t* la_E16 = nullptr;                 // bf16 models: the rounded L-A arrays
-  rmx::bf16_t* la_w16 = nullptr;
+  rmx::ScratchBuf<float> la_E;
+  rmx::ScratchBuf<float> la_w;
+  rmx::DevBuf<int64_t> la_rowptr;     // (row pointers: never in the scratch list, a leftover there would be an address)
+  rmx::ScratchBuf<float> la_out;
+  rmx::ScratchBuf<rmx::bf16_t> la_E16;           // bf16 models: the rounded L-A arrays
+  rmx::ScratchBuf<rmx::bf16_t> la_w16;
   int64_t la16_cap = 0;
   std::vector<int64_t> h_rowptr;
   std::vector<float> h_wperm;
@@ -144,8 +146,8 @@ struct rmx_model {
   rmx::TrainState* train = nullptr;          // backward (train.hip), created on first use
   struct LaGrad {                            // L-A backward staging (rmx_backward), grown on demand
     int64_t nnz = 0, B = 0, ml = 0;
-    float *gw = nullptr, *ge = nullptr, *gm = nullptr, *gb = nullptr, *tg = nullptr;
-    int32_t* idx = nullptr;
+    rmx::DevBuf<float> gw, ge, gm, gb, tg;
+    rmx::DevBuf<int32_t> idx;
   } la_grad;
 
   // ---- reentrancy (rmx.h "Threading"): one caller at a time; calls on different streams are
@@ -175,22 +177,22 @@ struct rmx_optim {
   int64_t steps = 0;
   int nslots = 0;                  // state slots per parameter: SGD 0, Momentum / Adagrad 1, Adam 2
   bool upd_w = false, upd_e = false;  // first order (not DNN) / embeddings (not LR)
-  float* w_s[2] = {nullptr, nullptr};   // [V]      per slot
-  float* e_s[2] = {nullptr, nullptr};   // [V][k]   per slot
-  float* m_s[2] = {nullptr, nullptr};   // [mats_len] per slot
-  float* b_s = nullptr;                 // [2] bias slots
-  float* hv = nullptr;                  // [rmx::kOptimHostVals] staging of the model's host-side values
+  rmx::DevBuf<float> w_s[2];            // [V]      per slot
+  rmx::DevBuf<float> e_s[2];            // [V][k]   per slot
+  rmx::DevBuf<float> m_s[2];            // [mats_len] per slot
+  rmx::DevBuf<float> b_s;               // [2] bias slots
+  rmx::DevBuf<float> hv;                // [rmx::kOptimHostVals] staging of the model's host-side values
   // grouping scratch, grown on demand (every word read by an apply is written by it first)
   int64_t cap_nnz = 0;
-  uint32_t* keys[2] = {nullptr, nullptr};
-  uint32_t* vals[2] = {nullptr, nullptr};
-  uint32_t* hist = nullptr;             // [256][tiles]
-  uint32_t* bsum = nullptr;             // sums of hist's 1,024-element blocks (the scan's first pass)
-  float* part = nullptr;                // [2 * windows][k + 1] chunk sums of lists longer than 512
-  int32_t* long_head = nullptr;         // [windows] start of the long list whose first chunk begins there
+  rmx::DevBuf<uint32_t> keys[2];
+  rmx::DevBuf<uint32_t> vals[2];
+  rmx::DevBuf<uint32_t> hist;           // [256][tiles]
+  rmx::DevBuf<uint32_t> bsum;           // sums of hist's 1,024-element blocks (the scan's first pass)
+  rmx::DevBuf<float> part;              // [2 * windows][k + 1] chunk sums of lists longer than 512
+  rmx::DevBuf<int32_t> long_head;       // [windows] start of the long list whose first chunk begins there
   // rmx_train_step_ids' gradients
   int64_t g_nnz = 0;
-  float *g_b = nullptr, *g_w = nullptr, *g_e = nullptr, *g_m = nullptr;  // g_b: [2] = {g_bias, loss}
+  rmx::DevBuf<float> g_b, g_w, g_e, g_m;  // g_b: [2] = {g_bias, loss}
 };
 
 namespace rmx {
@@ -223,8 +225,6 @@ int model_forward_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, b
                        float* out);
 int model_collect_timing(rmx_model& m);
 int model_ensure_ws(rmx_model& m, int B);  // inference workspace (y12, h, ...) for batches <= B
-void scratch_note(rmx_model& m, void* p, size_t bytes);
-void scratch_forget(rmx_model& m, void* p);
 int model_stage_host(rmx_model& m, int B, int64_t nnz, const int64_t* index, bool regular, bool sorted,
                      float bias, const float* weights, const float* embedding, const float* mats, FwdInputs* in);
 

@@ -103,27 +103,28 @@ struct rmx_shard {
   uint64_t owner_key = RMX_OWNER_HASH_DEFAULT;  // Feistel key of p (set_owner_hash); 0: owner = id mod N
   bool filled = false;                  // rows written (the owner function is then fixed)
   int rs = 0;                           // row stride in floats: [emb k | w | pad], one 128-B line at k < 32
-  std::vector<float*> part;             // partitions held here: [rows_per + 1][rs] (loopback: N); the
+  std::vector<rmx::DevBuf<float>> part;  // partitions held here: [rows_per + 1][rs] (loopback: N); the
                                         // extra row stays zero (the row of an out-of-range id read in place)
   // per-batch buffers (grow only)
   int64_t cap_send = 0, cap_recv = 0;
   int64_t cap_slot[2] = {0, 0};         // ids each pull slot's perm holds (grown one slot at a time)
   int64_t cap_rows[2] = {0, 0};         // rows each pull slot's recv_emb / recv_w hold
   int64_t cap_sfix = 0;                 // send_ids elements (max(nnz, N * cap))
-  int32_t* counts = nullptr;            // [4N]: send counts, recv counts, cursors, scratch
+  rmx::DevBuf<int32_t> counts;          // [4N]: send counts, recv counts, cursors, scratch
   int32_t* h_counts = nullptr;          // pinned host [2N]
-  int32_t* send_ids = nullptr;          // [nnz] local rows, bucketed by owner
-  int32_t* recv_ids = nullptr;          // [recv] local rows requested by the PEERS (own bucket excluded)
-  float* send_emb = nullptr;            // [recv][k] rows gathered for them
-  float* send_w = nullptr;              // [recv]
+  rmx::DevBuf<int32_t> send_ids;        // [nnz] local rows, bucketed by owner
+  rmx::DevBuf<int32_t> recv_ids;        // [recv] local rows requested by the PEERS (own bucket excluded)
+  rmx::DevBuf<float> send_emb;          // [recv][k] rows gathered for them
+  rmx::DevBuf<float> send_w;            // [recv]
   // the exchange's output, the forward's input: two pull slots (rmx_shard_pull / rmx_forward_pulled
   // overlap batch i + 1's exchange with batch i's forward); perm / recv_* point at the active slot
+  // (raw views of the active slot's perm_s / recv_emb_s / recv_w_s, never owned)
   int32_t* perm = nullptr;              // [nnz] slot of id n
   float* recv_emb = nullptr;            // [nnz][k] rows for this rank's batch (bucket order)
   float* recv_w = nullptr;              // [nnz]
-  int32_t* perm_s[2] = {nullptr, nullptr};
-  float* recv_emb_s[2] = {nullptr, nullptr};
-  float* recv_w_s[2] = {nullptr, nullptr};
+  rmx::DevBuf<int32_t> perm_s[2];
+  rmx::DevBuf<float> recv_emb_s[2];
+  rmx::DevBuf<float> recv_w_s[2];
   hipEvent_t ready[2] = {nullptr, nullptr};     // slot filled (recorded on the pull's stream)
   hipEvent_t consumed[2] = {nullptr, nullptr};  // slot read by its forward (on the forward's stream)
   bool consumed_rec[2] = {false, false};
@@ -137,13 +138,13 @@ struct rmx_shard {
   int dedupe = 2;
   int dedupe_skip = 0;
   int64_t cap_hash = 0;                 // hash-set slots (power of two >= 2 nnz)
-  int32_t* hkeys = nullptr;             // [cap_hash] distinct ids (-1 = empty)
-  int32_t* hvals = nullptr;             // [cap_hash] bucket slot of the distinct id
-  int32_t* hslot = nullptr;             // [nnz] set slot of id n
+  rmx::DevBuf<int32_t> hkeys;           // [cap_hash] distinct ids (-1 = empty)
+  rmx::DevBuf<int32_t> hvals;           // [cap_hash] bucket slot of the distinct id
+  rmx::DevBuf<int32_t> hslot;           // [nnz] set slot of id n
   mutable int64_t last_sent = 0;        // ids sent by the last exchange (distinct ids when deduped)
   mutable bool last_sent_dev = false;   // one rank: last_sent is still on the device (counts[0])
   mutable int last_fixed = -1;          // >= 0: last_sent is the summary of that slot's fixed exchange (pinned)
-  int32_t* bcnt = nullptr;              // [N][tiles] per-tile owner counts -> tile start offsets
+  rmx::DevBuf<int32_t> bcnt;            // [N][tiles] per-tile owner counts -> tile start offsets
   int64_t cap_tiles = 0;
   // Fixed-capacity exchange (N > 1 through a transport; knob "shard_fixed", default on): every peer bucket
   // has the host-known capacity cap (cap_of: ~1.1 nnz / N), so every message size is fixed and no count
@@ -157,11 +158,11 @@ struct rmx_shard {
   // rank reads the same maximum from its summary).  The first exchange has cap 0 (every id goes through
   // the counted overflow round) unless rmx_shard_set_batch_hint seeded it with the same value on every rank.
   int64_t cap_next = 0;
-  int32_t* send_ovf = nullptr;          // [cap_send] overflow ids in bucket order
-  int32_t* recv_fix = nullptr;          // [N][cap] ids requested by the peers
-  float* srow_emb = nullptr;            // [N][cap][k] rows gathered for the peers
-  float* srow_w = nullptr;              // [N][cap]
-  int32_t* hdr = nullptr;               // device: headers sent [N][3] | received [N][3] | summary [2N + 2]
+  rmx::DevBuf<int32_t> send_ovf;        // [cap_send] overflow ids in bucket order
+  rmx::DevBuf<int32_t> recv_fix;        // [N][cap] ids requested by the peers
+  rmx::DevBuf<float> srow_emb;          // [N][cap][k] rows gathered for the peers
+  rmx::DevBuf<float> srow_w;            // [N][cap]
+  rmx::DevBuf<int32_t> hdr;             // device: headers sent [N][3] | received [N][3] | summary [2N + 2]
   int32_t* h_hdr_s[2] = {nullptr, nullptr};   // pinned per pull slot: the summary (counts sent, received, any, max total)
   hipEvent_t hdr_ev[2] = {nullptr, nullptr};  // the slot's summary has reached the host
   bool unresolved[2] = {false, false};  // a fixed exchange whose overflow check is pending
@@ -170,9 +171,9 @@ struct rmx_shard {
   bool slot_dd[2] = {false, false};
   int64_t rounds2 = 0;                  // overflow rounds run so far
   int64_t cap_ovf = 0;                  // owner side of the overflow round (grown on demand)
-  int32_t* recv_ovf = nullptr;
-  float* ovf_emb = nullptr;
-  float* ovf_w = nullptr;
+  rmx::DevBuf<int32_t> recv_ovf;
+  rmx::DevBuf<float> ovf_emb;
+  rmx::DevBuf<float> ovf_w;
   // the overflow round runs on its slot's stream (shard_resolve), which need not be the stream of the
   // ShardUse that called it (rmx_forward_pulled resolves outside one): the next exchange's stream waits
   // on this event before its route rewrites send_ovf / the row scratch
@@ -611,17 +612,6 @@ __global__ void shard_fill_kernel(uint64_t seed, int64_t V, int64_t rows_per, in
 
 namespace {
 
-template <class T>
-int realloc_dev(T** p, int64_t n) {
-  if (*p) RMX_HIP(hipFree(*p));
-  *p = nullptr;
-  if (hipMalloc((void**)p, sizeof(T) * std::max<int64_t>(n, 1)) != hipSuccess) {
-    set_error("shard: out of device memory (" + std::to_string(n * (int64_t)sizeof(T)) + " bytes)");
-    return RMX_E_NOMEM;
-  }
-  return RMX_OK;
-}
-
 // [nnz]-sized buffers of this rank's batch: the exchange's scratch, and pull slot `slot` only.
 // The other slot may hold a pull its forward has not consumed (or is still reading): it is never
 // touched here.  The slot being grown has no pending pull (rmx_shard_pull refuses one), and the
@@ -639,8 +629,8 @@ int ensure_batch(rmx_shard& sh, int64_t nnz, int slot, int64_t nfix = 0) {
     int64_t hc = 1024;
     while (hc < 2 * n) hc <<= 1;
     const int64_t sf = std::max(std::max(n, nfix), sh.cap_sfix);
-    if ((st = realloc_dev(&sh.send_ids, sf)) || (st = realloc_dev(&sh.send_ovf, n)) ||
-        (st = realloc_dev(&sh.hslot, n)) || (st = realloc_dev(&sh.hkeys, hc)) || (st = realloc_dev(&sh.hvals, hc))) {
+    if ((st = sh.send_ids.alloc(sf, "shard")) || (st = sh.send_ovf.alloc(n, "shard")) ||
+        (st = sh.hslot.alloc(n, "shard")) || (st = sh.hkeys.alloc(hc, "shard")) || (st = sh.hvals.alloc(hc, "shard"))) {
       sh.cap_send = sh.cap_hash = sh.cap_sfix = 0;
       return st;
     }
@@ -650,8 +640,8 @@ int ensure_batch(rmx_shard& sh, int64_t nnz, int slot, int64_t nfix = 0) {
   }
   if (nnz > sh.cap_slot[slot] || nrows > sh.cap_rows[slot]) {
     const int64_t n = std::max(nnz, sh.cap_slot[slot]), r = std::max(nrows, sh.cap_rows[slot]);
-    if ((st = realloc_dev(&sh.perm_s[slot], n)) || (st = realloc_dev(&sh.recv_emb_s[slot], r * sh.k)) ||
-        (st = realloc_dev(&sh.recv_w_s[slot], r))) {
+    if ((st = sh.perm_s[slot].alloc(n, "shard")) || (st = sh.recv_emb_s[slot].alloc(r * sh.k, "shard")) ||
+        (st = sh.recv_w_s[slot].alloc(r, "shard"))) {
       sh.cap_slot[slot] = sh.cap_rows[slot] = 0;
       return st;
     }
@@ -666,8 +656,8 @@ int ensure_fixed(rmx_shard& sh, int64_t nfix) {
   if (nfix <= sh.cap_fix) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());  // a peer's copy of the old rows may still be in flight
   int st;
-  if ((st = realloc_dev(&sh.recv_fix, nfix)) || (st = realloc_dev(&sh.srow_emb, nfix * sh.k)) ||
-      (st = realloc_dev(&sh.srow_w, nfix))) {
+  if ((st = sh.recv_fix.alloc(nfix, "shard")) || (st = sh.srow_emb.alloc(nfix * sh.k, "shard")) ||
+      (st = sh.srow_w.alloc(nfix, "shard"))) {
     sh.cap_fix = 0;
     return st;
   }
@@ -680,8 +670,8 @@ int ensure_ovf(rmx_shard& sh, int64_t n) {
   if (n <= sh.cap_ovf) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
   int st;
-  if ((st = realloc_dev(&sh.recv_ovf, n)) || (st = realloc_dev(&sh.ovf_emb, n * sh.k)) ||
-      (st = realloc_dev(&sh.ovf_w, n))) {
+  if ((st = sh.recv_ovf.alloc(n, "shard")) || (st = sh.ovf_emb.alloc(n * sh.k, "shard")) ||
+      (st = sh.ovf_w.alloc(n, "shard"))) {
     sh.cap_ovf = 0;
     return st;
   }
@@ -694,7 +684,7 @@ int ensure_tiles(rmx_shard& sh, int64_t tiles) {
   if (tiles <= sh.cap_tiles) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
   int st;
-  if ((st = realloc_dev(&sh.bcnt, tiles * sh.N))) return st;
+  if ((st = sh.bcnt.alloc(tiles * sh.N, "shard"))) return st;
   sh.cap_tiles = tiles;
   return RMX_OK;
 }
@@ -704,8 +694,8 @@ int ensure_recv(rmx_shard& sh, int64_t n) {
   if (n <= sh.cap_recv) return RMX_OK;
   int st;
   RMX_HIP(hipDeviceSynchronize());  // a peer's copy of the old rows may still be in flight
-  if ((st = realloc_dev(&sh.recv_ids, n)) || (st = realloc_dev(&sh.send_emb, n * sh.k)) ||
-      (st = realloc_dev(&sh.send_w, n))) {
+  if ((st = sh.recv_ids.alloc(n, "shard")) || (st = sh.send_emb.alloc(n * sh.k, "shard")) ||
+      (st = sh.send_w.alloc(n, "shard"))) {
     sh.cap_recv = 0;
     return st;
   }
@@ -970,18 +960,15 @@ int shard_create(rmx_ctx* ctx, int64_t V, int k, int N, int rank, const void* un
   sh->rows_per = (V + N - 1) / N;
   sh->rs = (k + 1 + 31) / 32 * 32;  // [emb | w | pad]: a 128-B line per row for k < 32
   const int parts = sh->loopback ? N : 1;
+  int st;
   for (int p = 0; p < parts; ++p) {
-    float* r = nullptr;
-    if (hipMalloc(&r, sizeof(float) * (sh->rows_per + 1) * sh->rs) != hipSuccess) {
-      for (float* q : sh->part) (void)hipFree(q);
-      set_error("rmx_shard_create: out of device memory for the partition");
-      return RMX_E_NOMEM;
-    }
-    sh->part.push_back(r);
+    sh->part.emplace_back();
+    if ((st = sh->part.back().alloc((size_t)(sh->rows_per + 1) * sh->rs, "rmx_shard_create (partition)")))
+      return st;
   }
-  RMX_HIP(hipMalloc(&sh->counts, sizeof(int32_t) * 4 * N));
+  if ((st = sh->counts.alloc(4 * N, "rmx_shard_create")) || (st = sh->hdr.alloc(8 * N + 2, "rmx_shard_create")))
+    return st;
   RMX_HIP(hipHostMalloc(&sh->h_counts, sizeof(int32_t) * 2 * N));
-  RMX_HIP(hipMalloc(&sh->hdr, sizeof(int32_t) * (8 * N + 2)));
   for (int q = 0; q < 2; ++q) {
     RMX_HIP(hipHostMalloc(&sh->h_hdr_s[q], sizeof(int32_t) * (2 * N + 2)));
     RMX_HIP(hipEventCreateWithFlags(&sh->hdr_ev[q], hipEventDisableTiming));
@@ -1022,15 +1009,7 @@ int shard_destroy(rmx_shard* sh) {
     }
     group_unref(sh->group);
   }
-  for (float* q : sh->part) (void)hipFree(q);
-  for (void* p : {(void*)sh->counts, (void*)sh->send_ids, (void*)sh->recv_ids, (void*)sh->send_emb, (void*)sh->send_w,
-                  (void*)sh->hkeys, (void*)sh->hvals, (void*)sh->hslot, (void*)sh->bcnt, (void*)sh->send_ovf,
-                  (void*)sh->recv_fix, (void*)sh->srow_emb, (void*)sh->srow_w, (void*)sh->hdr, (void*)sh->recv_ovf,
-                  (void*)sh->ovf_emb, (void*)sh->ovf_w})
-    if (p) (void)hipFree(p);
   for (int q = 0; q < 2; ++q) {
-    for (void* p : {(void*)sh->perm_s[q], (void*)sh->recv_emb_s[q], (void*)sh->recv_w_s[q]})
-      if (p) (void)hipFree(p);
     if (sh->ready[q]) (void)hipEventDestroy(sh->ready[q]);
     if (sh->consumed[q]) (void)hipEventDestroy(sh->consumed[q]);
     if (sh->hdr_ev[q]) (void)hipEventDestroy(sh->hdr_ev[q]);

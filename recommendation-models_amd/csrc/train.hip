@@ -31,72 +31,46 @@
 namespace rmx {
 
 struct TrainState {
-  rmx_model* owner = nullptr;   // (its scratch list records every buffer below but ones / onesR)
-  int B = 0;
+  rmx_model* owner = nullptr;   // (its scratch list records every ScratchBuf below; ones / onesR, written once
+  int B = 0;                    //  at allocation, stay out of it)
   int ldx = 0;                  // row stride of x / dx
-  float* x = nullptr;           // [B][ldx] tower input (Reshape(B, F*k) of the gathered rows)
-  std::vector<float*> h;        // per tower layer [B][Npad]
-  std::vector<float*> hm;       // per tower layer [B][16] ReLU mask bits (uint32), written by the row-owner
+  ScratchBuf<float> x;          // [B][ldx] tower input (Reshape(B, F*k) of the gathered rows)
+  std::vector<ScratchBuf<float>> h;   // per tower layer [B][Npad]
+  std::vector<ScratchBuf<float>> hm;  // per tower layer [B][16] ReLU mask bits (uint32), written by the row-owner
   std::vector<char> hm_ok;      //   forward kernels this step (k_layer_s3.hip / k_head_s3.hip XS); hm_ok: valid
-  float* g[2] = {nullptr, nullptr};  // [B][maxld] dPre / dx ping-pong
-  float* p = nullptr;           // [B] probabilities
-  float* dz = nullptr;          // [B] dL/dlogit
-  float* ones = nullptr;        // [B]
-  double* part = nullptr;       // [2 * kMaxParts] loss / dz partial sums
+  float* hm0 = nullptr;         // layer 1's bits: a view of fms's second half, borrowed, never owned (hm[0] stays empty)
+  float* mask_bits(size_t l) const { return l == 0 ? hm0 : hm[l].get(); }
+  ScratchBuf<float> g[2];       // [B][maxld] dPre / dx ping-pong
+  ScratchBuf<float> p;          // [B] probabilities
+  ScratchBuf<float> dz;         // [B] dL/dlogit
+  DevBuf<float> ones;           // [B]
+  ScratchBuf<double> part;      // [2 * kMaxParts] loss / dz partial sums
   // DCN (cross stack in closed form, k_interact.hip cross_finish_kernel)
-  float* xcol = nullptr;        // [B][L + 1] u_l = w_l . x0, v = W_out[0:D] . x0
-  float* wc = nullptr;          // [L + 1][D] rows w_0 .. w_{L-1}, W_out[0:D]
-  float* coef = nullptr;        // [B][L + 1] x0-coefficients of the cross gradients
-  float* cst = nullptr;         // [B][2L + 1] per-row constants (see cross_back_kernel)
-  float* gwc = nullptr;         // [L + 1][D] gradient of wc before the constant parts
-  float* tmp = nullptr;         // [max(Npad, 2L + 1)] column sums
+  ScratchBuf<float> xcol;       // [B][L + 1] u_l = w_l . x0, v = W_out[0:D] . x0
+  ScratchBuf<float> wc;         // [L + 1][D] rows w_0 .. w_{L-1}, W_out[0:D]
+  ScratchBuf<float> coef;       // [B][L + 1] x0-coefficients of the cross gradients
+  ScratchBuf<float> cst;        // [B][2L + 1] per-row constants (see cross_back_kernel)
+  ScratchBuf<float> gwc;        // [L + 1][D] gradient of wc before the constant parts
+  ScratchBuf<float> tmp;        // [max(Npad, 2L + 1)] column sums
   // xDeepFM CIN (rows r = b*k + j, R = B*k)
-  std::vector<float*> u;        // [R][Npad_l] maps of every CIN layer
-  float* x0 = nullptr;          // [R][F] x0[b*k + j][f] = e[b][f][j]
-  float* gx0 = nullptr;         // [R][F] dL/dx0 (CIN part)
-  float* gu[2] = {nullptr, nullptr};  // [R][maxNpad] dL/du of the layer below (from the layer above)
-  float* gpre = nullptr;        // [R][maxNpad] dL/d(pre-activation) of the current layer
-  float* dzr = nullptr;         // [R] dz[r / k]
-  float* zb = nullptr;          // [rc][max F*Hp] Z = x0 (x) u_prev chunk, then its gradient
-  float* onesR = nullptr;       // [R]
+  std::vector<ScratchBuf<float>> u;   // [R][Npad_l] maps of every CIN layer
+  ScratchBuf<float> x0;         // [R][F] x0[b*k + j][f] = e[b][f][j]
+  ScratchBuf<float> gx0;        // [R][F] dL/dx0 (CIN part)
+  ScratchBuf<float> gu[2];      // [R][maxNpad] dL/du of the layer below (from the layer above)
+  ScratchBuf<float> gpre;       // [R][maxNpad] dL/d(pre-activation) of the current layer
+  ScratchBuf<float> dzr;        // [R] dz[r / k]
+  ScratchBuf<float> zb;         // [rc][max F*Hp] Z = x0 (x) u_prev chunk, then its gradient
+  DevBuf<float> onesR;          // [R]
   int rc = 0;                   // rows per chunk (a multiple of k)
-  float* part2 = nullptr;       // [cap_part] slice partials of wgrad / colsum
+  ScratchBuf<float> part2;      // [cap_part] slice partials of wgrad / colsum
   int64_t cap_part = 0;
-  float* fms = nullptr;         // DeepFM, k = 16: [B][16] FM sums s_j of the forward (fused embedding gradient)
+  ScratchBuf<float> fms;        // DeepFM, k = 16: [B][16] FM sums s_j of the forward (fused embedding gradient)
   bool fms_valid = false;       // this step's forward wrote fms
 };
 
 namespace {
 
 constexpr int kRedThreads = 256, kMaxParts = 1024;
-
-template <class T>
-void tfree(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-int talloc(float** p, size_t n) {
-  if (hipMalloc((void**)p, sizeof(float) * std::max<size_t>(n, 1)) != hipSuccess) {
-    set_error("backward: out of device memory (" + std::to_string(n * sizeof(float)) + " bytes)");
-    return RMX_E_NOMEM;
-  }
-  return RMX_OK;
-}
-
-// scratch of the backward: allocated and recorded in the model's scratch list (rmx_debug_poison_workspace) /
-// forgotten and freed.  ones / onesR are written once at allocation and keep plain talloc / tfree
-int salloc(rmx_model& m, float** p, size_t n) {
-  const int st = talloc(p, n);
-  if (st == RMX_OK) scratch_note(m, *p, sizeof(float) * std::max<size_t>(n, 1));
-  return st;
-}
-
-template <class T>
-void sfree(rmx_model& m, T*& p) {
-  scratch_forget(m, p);
-  tfree(p);
-}
 
 __global__ void fill_kernel(int n, float v, float* __restrict__ y) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1371,9 +1345,8 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 int ensure_part(TrainState& T, int64_t n) {
   if (n <= T.cap_part) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
-  sfree(*T.owner, T.part2);
   T.cap_part = 0;
-  int st = salloc(*T.owner, &T.part2, (size_t)n);
+  int st = T.part2.alloc(T.owner->scratch, (size_t)n, "backward");
   if (st) return st;
   T.cap_part = n;
   return RMX_OK;
@@ -1612,58 +1585,30 @@ int ensure_train(rmx_model& m, int B, hipStream_t s) {
   T.owner = &m;
   if (B <= T.B) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
-  sfree(m, T.x);
-  for (auto& p : T.h) sfree(m, p);
-  T.h.clear();
-  for (size_t i = 1; i < T.hm.size(); ++i) sfree(m, T.hm[i]);  // (hm[0] is borrowed from fms, never owned)
-  T.hm.clear();
-  T.hm_ok.clear();
-  sfree(m, T.g[0]);
-  sfree(m, T.g[1]);
-  sfree(m, T.fms);
-  sfree(m, T.p);
-  sfree(m, T.dz);
-  tfree(T.ones);
-  sfree(m, T.tmp);
-  sfree(m, T.xcol);
-  sfree(m, T.wc);
-  sfree(m, T.coef);
-  sfree(m, T.cst);
-  sfree(m, T.gwc);
-  for (auto& p : T.u) sfree(m, p);
-  T.u.clear();
-  sfree(m, T.x0);
-  sfree(m, T.gx0);
-  sfree(m, T.gu[0]);
-  sfree(m, T.gu[1]);
-  sfree(m, T.gpre);
-  sfree(m, T.dzr);
-  sfree(m, T.zb);
-  tfree(T.onesR);
-  sfree(m, T.part2);
-  T.cap_part = 0;
-  sfree(m, T.part);
+  T = TrainState{};
+  T.owner = &m;
+  auto grow = [&m](ScratchBuf<float>& b, size_t n) { return b.alloc(m.scratch, n, "backward"); };
   int st;
   T.ldx = m.layers.empty() ? 0 : m.layers[0].Kpad;
   int maxld = std::max(T.ldx, 16);
-  if (!m.layers.empty() && (st = salloc(m, &T.x, (size_t)B * T.ldx))) return st;
+  if (!m.layers.empty() && (st = grow(T.x, (size_t)B * T.ldx))) return st;
   for (auto& L : m.layers) {
-    T.h.push_back(nullptr);
-    if ((st = salloc(m, &T.h.back(), (size_t)B * L.Npad))) return st;
-    T.hm.push_back(nullptr);
+    T.h.emplace_back();
+    if ((st = grow(T.h.back(), (size_t)B * L.Npad))) return st;
+    T.hm.emplace_back();
     T.hm_ok.push_back(0);
     // (layer 1's bits, from the training head, live in T.fms's second half)
-    if (T.h.size() > 1 && L.N == 400 && L.Npad == 416 && (st = salloc(m, &T.hm.back(), (size_t)B * 16))) return st;
+    if (T.h.size() > 1 && L.N == 400 && L.Npad == 416 && (st = grow(T.hm.back(), (size_t)B * 16))) return st;
     maxld = std::max(maxld, L.Npad);
   }
   if (!m.layers.empty()) {
-    if ((st = salloc(m, &T.g[0], (size_t)B * maxld))) return st;
-    if ((st = salloc(m, &T.g[1], (size_t)B * maxld))) return st;
+    if ((st = grow(T.g[0], (size_t)B * maxld))) return st;
+    if ((st = grow(T.g[1], (size_t)B * maxld))) return st;
   }
-  if ((st = salloc(m, &T.p, B)) || (st = salloc(m, &T.dz, B)) || (st = talloc(&T.ones, B))) return st;
+  if ((st = grow(T.p, B)) || (st = grow(T.dz, B)) || (st = T.ones.alloc(B, "backward"))) return st;
   // [2][B][16]: the FM sums, then (training head, k_head_s3.hip XS) h1's ReLU mask bits
-  if (m.type == RMX_MODEL_DEEPFM && m.k == 16 && (st = salloc(m, &T.fms, (size_t)B * 32))) return st;
-  if ((st = salloc(m, &T.tmp, std::max(maxld, 2 * m.cross_depth + 1)))) return st;
+  if (m.type == RMX_MODEL_DEEPFM && m.k == 16 && (st = grow(T.fms, (size_t)B * 32))) return st;
+  if ((st = grow(T.tmp, std::max(maxld, 2 * m.cross_depth + 1)))) return st;
   if (m.type == RMX_MODEL_XDEEPFM) {
     const int64_t R = (int64_t)B * m.k;
     int maxH = 16, maxFH = 16;
@@ -1672,31 +1617,27 @@ int ensure_train(rmx_model& m, int B, hipStream_t s) {
       maxFH = std::max(maxFH, std::max(m.F * c.Hp, c.NTpad));  // dz rows are NTpad wide (split GEMM)
     }
     for (auto& c : m.cin_layers) {
-      T.u.push_back(nullptr);
-      if ((st = salloc(m, &T.u.back(), (size_t)R * c.Npad))) return st;
+      T.u.emplace_back();
+      if ((st = grow(T.u.back(), (size_t)R * c.Npad))) return st;
     }
     const int64_t budget = 64ll << 20;  // floats of the Z chunk (256 MB)
     T.rc = (int)std::min<int64_t>(R, std::max<int64_t>(m.k, budget / maxFH / m.k * m.k));
-    if ((st = salloc(m, &T.x0, (size_t)R * m.F)) || (st = salloc(m, &T.gx0, (size_t)R * m.F)) ||
-        (st = salloc(m, &T.gu[0], (size_t)R * maxH)) || (st = salloc(m, &T.gu[1], (size_t)R * maxH)) ||
-        (st = salloc(m, &T.gpre, (size_t)R * maxH)) || (st = salloc(m, &T.dzr, R)) ||
-        (st = salloc(m, &T.zb, (size_t)T.rc * maxFH)) || (st = talloc(&T.onesR, R)))
+    if ((st = grow(T.x0, (size_t)R * m.F)) || (st = grow(T.gx0, (size_t)R * m.F)) ||
+        (st = grow(T.gu[0], (size_t)R * maxH)) || (st = grow(T.gu[1], (size_t)R * maxH)) ||
+        (st = grow(T.gpre, (size_t)R * maxH)) || (st = grow(T.dzr, R)) ||
+        (st = grow(T.zb, (size_t)T.rc * maxFH)) || (st = T.onesR.alloc(R, "backward")))
       return st;
     hipLaunchKernelGGL(fill_kernel, dim3(nblk(R)), dim3(256), 0, s, (int)R, 1.0f, T.onesR);
     RMX_HIP(hipGetLastError());
   }
   if (m.type == RMX_MODEL_DCN) {
     const int L = m.cross_depth, D = m.F * m.k;
-    if ((st = salloc(m, &T.xcol, (size_t)B * (L + 1))) || (st = salloc(m, &T.wc, (size_t)(L + 1) * D)) ||
-        (st = salloc(m, &T.coef, (size_t)B * (L + 1))) || (st = salloc(m, &T.cst, (size_t)B * (2 * L + 1))) ||
-        (st = salloc(m, &T.gwc, (size_t)(L + 1) * D)))
+    if ((st = grow(T.xcol, (size_t)B * (L + 1))) || (st = grow(T.wc, (size_t)(L + 1) * D)) ||
+        (st = grow(T.coef, (size_t)B * (L + 1))) || (st = grow(T.cst, (size_t)B * (2 * L + 1))) ||
+        (st = grow(T.gwc, (size_t)(L + 1) * D)))
       return st;
   }
-  if (hipMalloc(&T.part, sizeof(double) * 2 * kMaxParts) != hipSuccess) {
-    set_error("backward: out of device memory");
-    return RMX_E_NOMEM;
-  }
-  scratch_note(m, T.part, sizeof(double) * 2 * kMaxParts);
+  if ((st = T.part.alloc(m.scratch, 2 * kMaxParts, "backward"))) return st;
   hipLaunchKernelGGL(fill_kernel, dim3(nblk(B)), dim3(256), 0, s, B, 1.0f, T.ones);
   RMX_HIP(hipGetLastError());
   T.B = B;
@@ -1707,34 +1648,7 @@ int ensure_train(rmx_model& m, int B, hipStream_t s) {
 
 void train_release(rmx_model& m) {
   if (!m.train) return;
-  TrainState& T = *m.train;
   (void)hipDeviceSynchronize();
-  sfree(m, T.x);
-  for (auto& p : T.h) sfree(m, p);
-  for (size_t i = 1; i < T.hm.size(); ++i) sfree(m, T.hm[i]);  // (hm[0] is borrowed from fms, never owned)
-  sfree(m, T.g[0]);
-  sfree(m, T.g[1]);
-  sfree(m, T.fms);
-  sfree(m, T.p);
-  sfree(m, T.dz);
-  tfree(T.ones);
-  sfree(m, T.tmp);
-  sfree(m, T.xcol);
-  sfree(m, T.wc);
-  sfree(m, T.coef);
-  sfree(m, T.cst);
-  sfree(m, T.gwc);
-  for (auto& p : T.u) sfree(m, p);
-  sfree(m, T.x0);
-  sfree(m, T.gx0);
-  sfree(m, T.gu[0]);
-  sfree(m, T.gu[1]);
-  sfree(m, T.gpre);
-  sfree(m, T.dzr);
-  sfree(m, T.zb);
-  tfree(T.onesR);
-  sfree(m, T.part2);
-  sfree(m, T.part);
   delete m.train;
   m.train = nullptr;
 }
@@ -1791,27 +1705,27 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
       StageTimer tm(m, s, "head_x");
       T.fms_valid = true;
       if ((st = launch_tower_head_s3(s, m.layers[0], B, F, in.ids, (const float*)in.table, 0, (const float*)in.wtab, 0,
-                                     T.h[0], m.layers[0].Npad, m.y12, 1, T.x, T.ldx, T.fms)))
+                                     T.h[0], m.layers[0].Npad, m.ws.y12, 1, T.x, T.ldx, T.fms)))
         return st;
-      T.hm[0] = T.fms + (int64_t)B * 16;  // (not owned: see ensure_train)
+      T.hm0 = T.fms + (int64_t)B * 16;  // (not owned: see TrainState)
       T.hm_ok[0] = 1;
-      pre = m.y12;
+      pre = m.ws.y12;
     } else if (t == RMX_MODEL_DEEPFM) {
       StageTimer tm(m, s, fuse_x ? "encoder_fm_x" : "encoder_fm");
       // the FM sums for the fused embedding gradient (knob "train_emb_fused", default on)
       T.fms_valid = T.fms && k == 16 && tuning_get("train_emb_fused", 1) != 0;
-      if ((st = launch_encoder(s, in.y1 ? 3 : 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr,
+      if ((st = launch_encoder(s, in.y1 ? 3 : 1, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.ws.y12, nullptr,
                                nullptr, 0, 0, xo, T.fms_valid ? T.fms : nullptr)))
         return st;
-      pre = m.y12;
+      pre = m.ws.y12;
     } else if (t != RMX_MODEL_DNN) {
       if (!in.y1) {
         StageTimer tm(m, s, fuse_x ? "first_order_x" : "first_order");
-        if ((st = launch_encoder(s, 0, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.y12, nullptr, nullptr, 0, 0,
+        if ((st = launch_encoder(s, 0, B, in.ids, in.table, in.wtab, in.dtype, F, k, m.ws.y12, nullptr, nullptr, 0, 0,
                                  xo)))
           return st;
       }
-      pre = m.y12;
+      pre = m.ws.y12;
     }
     if (t == RMX_MODEL_PNN) {
       StageTimer tm(m, s, "product");
@@ -1827,7 +1741,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
         StageTimer tm(m, s, l == 0 ? "cin_layer1" : (l == 1 ? "cin_layer2" : "cin_layer3+"));
         // last = false: every layer's maps are stored (the backward needs them)
         if ((st = launch_cin_layer(s, m.cin_layers[l], l == 0, false, B, F, k, in.ids, (const float*)in.table, uprev,
-                                   T.u[l], m.rowdot)))
+                                   T.u[l], m.ws.rowdot)))
           return st;
         uprev = T.u[l];
       }
@@ -1846,7 +1760,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
       const bool fused = i == 0 && m.dcn_fused;
       if (i > 0 && layer_s3_usable(L, false, B, lda, L.Npad)) {
         // 400 x 400 hidden layers: the row-owner kernel (k_layer_s3.hip; knob "train_layer_s3")
-        uint32_t* hmi = reinterpret_cast<uint32_t*>(T.hm[i]);
+        uint32_t* hmi = reinterpret_cast<uint32_t*>(T.hm[i].get());
         if ((st = launch_layer_s3(s, L, false, B, A, lda, T.h[i], L.Npad, hmi, nullptr))) return st;
         T.hm_ok[i] = hmi ? 1 : 0;
       } else if ((st = launch_tower_layer(s, L, B, A, lda, nullptr, T.h[i], L.Npad, Epi::kReluStore, nullptr,
@@ -1864,11 +1778,11 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
       RMX_HIP(hipMemcpyAsync(T.wc + (int64_t)Lc * D, m.wo_x, sizeof(float) * D, hipMemcpyDeviceToDevice, s));
       if (!m.dcn_fused && (st = launch_gemm_f32(s, true, false, B, Lc + 1, D, T.x, T.ldx, T.wc, D, T.xcol, Lc + 1)))
         return st;
-      if ((st = launch_cross_finish(s, B, Lc, T.xcol, m.cross_scalars, m.pre2))) return st;
-      oa.pre2 = m.pre2;
+      if ((st = launch_cross_finish(s, B, Lc, T.xcol, m.cross_scalars, m.ws.pre2))) return st;
+      oa.pre2 = m.ws.pre2;
     }
     if (t == RMX_MODEL_XDEEPFM) {
-      oa.rowsum = m.rowdot;
+      oa.rowsum = m.ws.rowdot;
       oa.rowsum_k = k;
     }
     oa.wo = m.wo;
@@ -1955,8 +1869,8 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
     if (o.g_mats && (st = colsum(T, s, B, N, T.h[nl - 1], last.Npad, T.dz, o.g_mats + m.wo_off, false))) return st;
     if (N % 4 == 0 && last.Npad % 4 == 0)
       hipLaunchKernelGGL(head_back4_kernel, dim3(nblk((int64_t)B * (N / 4))), dim3(256), 0, s, B, N / 4,
-                         reinterpret_cast<const float4*>(T.h[nl - 1]), last.Npad / 4, T.dz,
-                         reinterpret_cast<const float4*>(m.wo), reinterpret_cast<float4*>(T.g[0]), last.Npad / 4);
+                         reinterpret_cast<const float4*>(T.h[nl - 1].get()), last.Npad / 4, T.dz,
+                         reinterpret_cast<const float4*>(m.wo.get()), reinterpret_cast<float4*>(T.g[0].get()), last.Npad / 4);
     else
       hipLaunchKernelGGL(head_back_kernel, dim3(nblk((int64_t)B * N)), dim3(256), 0, s, B, N, T.h[nl - 1], last.Npad,
                          T.dz, m.wo, T.g[0], last.Npad);
@@ -2007,7 +1921,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
         } else if (mask && T.hm_ok[l - 1] && bk.c0 == 0 && layer_s3_usable(L, true, B, L.Npad, ldin)) {
           // 400 x 400 layers whose lower layer left its mask bits: the row-owner kernel (k_layer_s3.hip)
           if ((st = launch_layer_s3(s, L, true, B, dpre, L.Npad, dxin, ldin, nullptr,
-                                    reinterpret_cast<const uint32_t*>(T.hm[l - 1]))))
+                                    reinterpret_cast<const uint32_t*>(T.mask_bits(l - 1)))))
             return st;
         } else if ((st = launch_dx_s3(s, L, B, dpre, L.Npad, dxin + bk.c0, ldin, mask, ldmask))) {
           return st;

@@ -450,6 +450,13 @@ def debug_poison_workspace(model, pattern=0x7FC07FC0, stream=None):
     return int(n.value)
 
 
+def debug_live_device_memory():
+    """Test hook: (bytes, buffers) of device memory the library's objects hold right now in this process."""
+    b, n = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.lib.rmx_debug_live_device_memory(ctypes.byref(b), ctypes.byref(n)))
+    return int(b.value), int(n.value)
+
+
 # ------------------------------------------------------------------ models ---
 class RecModel:
     """abstract class RecModel(type) -- yr/model/RecModel.scala:6-127."""
