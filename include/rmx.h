@@ -224,7 +224,17 @@ int rmx_backward_ids(rmx_model* m, const rmx_table* t, int32_t batch, const int3
  * occurrences is summed in consecutive chunks of 512 in that order, and the chunk sums are then added in chunk
  * order.  No float atomics: results are bitwise repeatable and independent of the launch geometry.  Ids outside
  * [0, V) are skipped and never addressed.
- * fp32 models and fp32 tables only (RMX_E_INVALID otherwise; sharded tables are out of scope); host-only model,
+ * Sharded summation order (a contract, rmx_optim_create_sharded below): one step on a shard over ranks 0..N-1 is,
+ * bit for bit, rmx_optim_apply on a replicated table given the ranks' batches concatenated in ascending rank order
+ * (ids, g_weights and g_embedding concatenated) -- for the table rows and their state.  An id's gradient is the
+ * fp32 sum of its occurrences in ascending (rank, nonzero) order, long lists in the same chunks of 512; ids outside
+ * [0, V) are skipped and never addressed, and a partition's zero row stays zero; t is one per apply.  The mats and
+ * bias gradients are the fp32 sums of the ranks' gradients, added in ascending rank order starting from rank 0's,
+ * then pushed through the same elementwise update and repack: every rank computes the same bits, so the
+ * replicas' mats, bias and host-side copies stay identical without a broadcast.  Gradients are SUMMED over the
+ * ranks, not averaged (the reference applies every worker's push at full weight): a caller who wants the global
+ * mean scales eta.  No float atomics here either.
+ * fp32 models and fp32 tables only (RMX_E_INVALID otherwise); host-only model,
  * NULL arguments, unknown kind, a negative or non-finite eta: RMX_E_INVALID; table k != model k: RMX_E_SHAPE.
  * Every check runs before any device call. */
 typedef struct rmx_optim rmx_optim;
@@ -411,6 +421,41 @@ int rmx_forward_ids_sharded(rmx_model* m, rmx_shard* sh, int32_t batch, const in
  * A slot holds one pull until its forward consumes it (a second pull into it fails RMX_E_INVALID). */
 int rmx_shard_pull(rmx_shard* sh, int64_t n, const int32_t* d_ids, int slot, void* stream);
 int rmx_forward_pulled(rmx_model* m, rmx_shard* sh, int32_t batch, int slot, float* d_out, void* stream);
+/* Training on the sharded table: the reference's optimize* (ParRecModel.scala:348-517) is pull, forward and
+ * backward, then push to the partitioned PS matrices (pushWeightBiasEmbeddingMats, :225-253).
+ * rmx_backward_pulled: the counterpart of rmx_forward_pulled -- one training pass (rmx_backward_ids' outputs and
+ * layout: per nonzero of this rank's batch, the loss the mean BCE over its `batch` rows) over the rows in the pull
+ * slot, which it consumes.  Same checks as rmx_forward_pulled (empty slot RMX_E_INVALID, another id count
+ * RMX_E_SHAPE, model not fp32 RMX_E_INVALID, k mismatch RMX_E_SHAPE).  Every output equals rmx_backward_ids on a
+ * replicated table holding the same rows, bit for bit, with the pull's dedupe on or off. */
+int rmx_backward_pulled(rmx_model* m, rmx_shard* sh, int32_t batch, int slot, const float* d_targets,
+                        float* d_g_bias, float* d_g_weights, float* d_g_embedding, float* d_g_mats,
+                        float* d_loss, void* stream);
+/* The push: an optimiser on a shard (the same rmx_optim type; rmx_optim_destroy before its model and shard,
+ * rmx_optim_steps, and the mats / bias outputs of rmx_optim_state_ptrs work as for a table; its d_weights /
+ * d_embedding outputs are NULL).  Argument checks as rmx_optim_create with the shard in the table's place, all
+ * before any device or collective call.  State: zero-initialised [local rows][k] and [local rows] per partition
+ * held here (a loopback shard holds nranks), mats_len and 1 as for a table; rmx_optim_shard_state_ptrs returns
+ * partition `part`'s (0, except on a loopback shard), indexed by the local row of rmx_owner_hash.
+ * rmx_optim_apply on such an optimiser is COLLECTIVE: every rank calls it for the same step with its own batch's
+ * ids and per-nonzero gradients, the same groups NULL or non-NULL on every rank.  The result is fixed by the
+ * sharded summation order above.  Protocol (csrc/shard.hip): the nonzeros bucketed by owner in
+ * nonzero order, bucket sizes to the peers and ONE host sync on them (as the counted pull), the rows to their
+ * owners, the replicated table's ordered sum and update there; g_mats / g_bias to every peer, added in rank order.
+ * A failed collective leaves the shard failed as a failed pull does (rmx_shard_abort, then a new shard).  One rank:
+ * no exchange and no host sync beyond rmx_optim_apply's own.
+ * rmx_train_step_sharded (collective): pull into slot 0 (which must be free), rmx_backward_pulled into
+ * optimiser-owned buffers, apply; synchronous on return; *loss (host, nullable) = this rank's own mean BCE.
+ * rmx_train_step_ids with a sharded optimiser, and rmx_train_step_sharded with a table's optimiser or another
+ * shard's, fail with RMX_E_INVALID before any device call.
+ * Out of scope: bf16, pre-aggregating per distinct id before the send (another summation order), a
+ * fixed-capacity sync-free push, a host upload into a shard.  The RCCL transport at nranks > 1 has not been
+ * executed for the push either (it uses the pull's grouped send / recv only). */
+int rmx_optim_create_sharded(rmx_model* m, rmx_shard* sh, int kind, const double* hyper, int n_hyper,
+                             rmx_optim** out);
+int rmx_optim_shard_state_ptrs(const rmx_optim* o, int part, int slot, void** d_weights, void** d_embedding);
+int rmx_train_step_sharded(rmx_model* m, rmx_shard* sh, rmx_optim* o, int32_t batch, const int32_t* d_ids,
+                           const float* d_targets, float* loss, void* stream);
 
 /* ---- samples: native LIBSVM / LIBFFM parser (host, multi-threaded) ----
  * Replaces SampleParser.parse (yr/data/SampleParser.scala:14-85) for text in memory (one sample per

@@ -662,23 +662,25 @@ extern "C" int rmx_backward_ids(rmx_model* m, const rmx_table* t, int32_t B, con
 }
 
 // ------------------------------------------------------------ optimiser --
-extern "C" int rmx_optim_create(rmx_model* m, rmx_table* t, int kind, const double* hyper, int n_hyper,
-                                rmx_optim** out) {
-  CHECK_ARG(out, "rmx_optim_create: out is NULL");
-  CHECK_ARG(m, "rmx_optim_create: model is NULL");
-  if (kind < RMX_OPTIM_SGD || kind > RMX_OPTIM_ADAM) {
-    set_error("rmx_optim_create: unknown optimiser kind " + std::to_string(kind));
-    return RMX_E_INVALID;
-  }
+int rmx::optim_new(const char* who_c, rmx_model* m, int kind, const double* hyper, int n_hyper, rmx_optim** out) {
+  const std::string who = std::string(who_c) + ": ";
+#define CHECK_WHO(cond, msg)    \
+  do {                          \
+    if (!(cond)) {              \
+      set_error(who + (msg));   \
+      return RMX_E_INVALID;     \
+    }                           \
+  } while (0)
+  CHECK_WHO(out, "out is NULL");
+  CHECK_WHO(m, "model is NULL");
+  CHECK_WHO(kind >= RMX_OPTIM_SGD && kind <= RMX_OPTIM_ADAM, "unknown optimiser kind " + std::to_string(kind));
   static const int kMaxHyper[4] = {1, 2, 3, 4};
-  CHECK_ARG(hyper && n_hyper >= 1, "rmx_optim_create: hyper needs at least eta");
-  if (n_hyper > kMaxHyper[kind]) {
-    set_error("rmx_optim_create: kind " + std::to_string(kind) + " takes at most " + std::to_string(kMaxHyper[kind]) +
-              " hyper-parameters, got " + std::to_string(n_hyper));
-    return RMX_E_INVALID;
-  }
-  for (int i = 0; i < n_hyper; ++i) CHECK_ARG(std::isfinite(hyper[i]), "rmx_optim_create: non-finite hyper-parameter");
-  CHECK_ARG(hyper[0] >= 0.0, "rmx_optim_create: eta is negative");
+  CHECK_WHO(hyper && n_hyper >= 1, "hyper needs at least eta");
+  CHECK_WHO(n_hyper <= kMaxHyper[kind], "kind " + std::to_string(kind) + " takes at most " +
+                                            std::to_string(kMaxHyper[kind]) + " hyper-parameters, got " +
+                                            std::to_string(n_hyper));
+  for (int i = 0; i < n_hyper; ++i) CHECK_WHO(std::isfinite(hyper[i]), "non-finite hyper-parameter");
+  CHECK_WHO(hyper[0] >= 0.0, "eta is negative");
   auto hp = [&](int i, double def) { return i < n_hyper ? hyper[i] : def; };
   std::unique_ptr<rmx_optim> o(new rmx_optim());
   o->kind = kind;
@@ -689,10 +691,24 @@ extern "C" int rmx_optim_create(rmx_model* m, rmx_table* t, int kind, const doub
     case RMX_OPTIM_ADAM: o->b = hp(1, 0.99); o->a = hp(2, 0.9); o->eps = hp(3, 1e-7); o->nslots = 2; break;
     default: break;
   }
-  CHECK_ARG(o->a >= 0.0 && o->a <= 1.0 && o->b >= 0.0 && o->b <= 1.0 && o->eps >= 0.0,
-            "rmx_optim_create: momentum / factor / gamma / beta must lie in [0, 1], eps must not be negative");
-  CHECK_ARG(kind != RMX_OPTIM_ADAM || (o->a < 1.0 && o->b < 1.0), "rmx_optim_create: Adam needs beta, gamma < 1");
-  CHECK_ARG(m->ctx, "rmx_optim_create: host-only model (created without a context)");
+  CHECK_WHO(o->a >= 0.0 && o->a <= 1.0 && o->b >= 0.0 && o->b <= 1.0 && o->eps >= 0.0,
+            "momentum / factor / gamma / beta must lie in [0, 1], eps must not be negative");
+  CHECK_WHO(kind != RMX_OPTIM_ADAM || (o->a < 1.0 && o->b < 1.0), "Adam needs beta, gamma < 1");
+  CHECK_WHO(m->ctx, "host-only model (created without a context)");
+#undef CHECK_WHO
+  o->m = m;
+  o->upd_w = m->type != RMX_MODEL_DNN;
+  o->upd_e = m->type != RMX_MODEL_LR;
+  *out = o.release();
+  return RMX_OK;
+}
+
+extern "C" int rmx_optim_create(rmx_model* m, rmx_table* t, int kind, const double* hyper, int n_hyper,
+                                rmx_optim** out) {
+  rmx_optim* raw = nullptr;
+  int st = optim_new("rmx_optim_create", m, kind, hyper, n_hyper, out ? &raw : nullptr);
+  if (st) return st;
+  std::unique_ptr<rmx_optim> o(raw);
   CHECK_ARG(t, "rmx_optim_create: table is NULL");
   CHECK_ARG(m->precision == RMX_DTYPE_F32, "rmx_optim_create: fp32 models only");
   CHECK_ARG(t->dtype == RMX_DTYPE_F32, "rmx_optim_create: fp32 tables only");
@@ -700,12 +716,10 @@ extern "C" int rmx_optim_create(rmx_model* m, rmx_table* t, int kind, const doub
     set_error("rmx_optim_create: table embedding_dim " + std::to_string(t->k) + " != model " + std::to_string(m->k));
     return RMX_E_SHAPE;
   }
-  o->m = m;
   o->t = t;
-  o->upd_w = m->type != RMX_MODEL_DNN;
-  o->upd_e = m->type != RMX_MODEL_LR;
-  const int st = optim_alloc(*o);
-  if (st) return st;
+  o->k = t->k;
+  o->rows = t->V;
+  if ((st = optim_alloc(*o))) return st;
   *out = o.release();
   return RMX_OK;
 }
@@ -723,10 +737,24 @@ extern "C" int rmx_optim_state_ptrs(const rmx_optim* o, int slot, void** d_weigh
                                     void** d_bias) {
   CHECK_ARG(o && slot >= 0 && slot < 2, "rmx_optim_state_ptrs: bad args");
   const bool has = slot < o->nslots;
-  if (d_weights) *d_weights = has ? o->w_s[slot] : nullptr;
-  if (d_embedding) *d_embedding = has ? o->e_s[slot] : nullptr;
+  // (a sharded optimiser's table state is per partition: rmx_optim_shard_state_ptrs)
+  if (d_weights) *d_weights = has && !o->sh ? o->w_s[slot] : nullptr;
+  if (d_embedding) *d_embedding = has && !o->sh ? o->e_s[slot] : nullptr;
   if (d_mats) *d_mats = has ? o->m_s[slot] : nullptr;
   if (d_bias) *d_bias = has ? o->b_s + slot : nullptr;
+  return RMX_OK;
+}
+
+extern "C" int rmx_optim_shard_state_ptrs(const rmx_optim* o, int part, int slot, void** d_weights,
+                                          void** d_embedding) {
+  CHECK_ARG(o && slot >= 0 && slot < 2, "rmx_optim_shard_state_ptrs: bad args");
+  CHECK_ARG(o->sh, "rmx_optim_shard_state_ptrs: the optimiser holds a table, not a shard");
+  CHECK_ARG(part >= 0 && part < o->nparts, "rmx_optim_shard_state_ptrs: no such partition here");
+  const bool has = slot < o->nslots;
+  float* w = o->w_s[slot];
+  float* e = o->e_s[slot];
+  if (d_weights) *d_weights = has && w ? w + (size_t)part * o->rows : nullptr;
+  if (d_embedding) *d_embedding = has && e ? e + (size_t)part * o->rows * o->k : nullptr;
   return RMX_OK;
 }
 
@@ -758,6 +786,7 @@ extern "C" int rmx_optim_apply(rmx_optim* o, int32_t B, const int32_t* d_ids, co
   rmx_model* m = o->m;
   RMX_HIP(hipSetDevice(m->ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : m->ctx->stream;
+  if (o->sh) return shard_optim_apply(*o, s, B, d_ids, d_g_bias, d_g_weights, d_g_embedding, d_g_mats);
   ModelUse use(*m, s);
   if (use.st) return use.st;
   return optim_apply(*o, s, B, d_ids, d_g_bias, d_g_weights, d_g_embedding, d_g_mats, nullptr, nullptr, false);
@@ -766,6 +795,7 @@ extern "C" int rmx_optim_apply(rmx_optim* o, int32_t B, const int32_t* d_ids, co
 extern "C" int rmx_train_step_ids(rmx_model* m, const rmx_table* t, rmx_optim* o, int32_t B, const int32_t* d_ids,
                                   const float* d_targets, float* loss, void* stream) {
   CHECK_ARG(m && t && o, "rmx_train_step_ids: bad args");
+  CHECK_ARG(!o->sh, "rmx_train_step_ids: the optimiser holds a shard (rmx_train_step_sharded)");
   CHECK_ARG(o->m == m && o->t == t, "rmx_train_step_ids: the optimiser belongs to another model / table");
   CHECK_ARG(d_targets || B == 0, "rmx_train_step_ids: targets is NULL");
   int st = optim_ready("rmx_train_step_ids", o, B, d_ids);

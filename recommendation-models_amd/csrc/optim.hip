@@ -67,6 +67,20 @@ __device__ __forceinline__ void pv_store(const PVal& v, float* p, float* s1, flo
   if (s1) s1[i] = v.s1;
   if (s2) s2[i] = v.s2;
 }
+// the same with the parameter at ip and its state at is (the [emb | w | pad] line rows of a shard partition: the
+// state slots stay dense)
+__device__ __forceinline__ PVal pv_load(const float* p, const float* s1, const float* s2, size_t ip, size_t is) {
+  PVal v;
+  v.p = p[ip];
+  v.s1 = s1 ? s1[is] : 0.f;
+  v.s2 = s2 ? s2[is] : 0.f;
+  return v;
+}
+__device__ __forceinline__ void pv_store(const PVal& v, float* p, float* s1, float* s2, size_t ip, size_t is) {
+  p[ip] = v.p;
+  if (s1) s1[is] = v.s1;
+  if (s2) s2[is] = v.s2;
+}
 
 // ------------------------------------------------------------------ radix sort ----
 constexpr int kRsThreads = 256, kRsItems = 16, kRsTile = kRsThreads * kRsItems, kRsBins = 256;
@@ -225,6 +239,14 @@ struct TabArgs {
   float* part;         // [2 * windows][k + 1]
   int32_t* long_head;  // [windows]
   Hyper h;
+  static constexpr bool kLines = false;
+};
+// the same for the [emb k | w | pad] line rows of a shard partition (w: the w slot of row 0): the parameters
+// take the row stride rs, the state slots stay dense.  A type of its own, so that the replicated table's
+// kernels keep their arguments and their code.
+struct LineArgs : TabArgs {
+  int rs;  // row stride in floats
+  static constexpr bool kLines = true;
 };
 
 // Adds the gradient rows of 8 list positions, in order, to se / sw: position r0 + r of a 16-position window is
@@ -274,18 +296,41 @@ __device__ __forceinline__ void sum_list(const TabArgs& a, int p, int cnt, int g
   }
 }
 
+// the parameters of row `key` with their state, loaded and stored (A: TabArgs or LineArgs, fixed at compile time)
+template <class A>
+__device__ __forceinline__ PVal load_emb(const A& a, uint32_t key, int col) {
+  if constexpr (A::kLines) return pv_load(a.emb, a.es1, a.es2, (size_t)key * a.rs + col, (size_t)key * a.k + col);
+  else return pv_load(a.emb, a.es1, a.es2, (size_t)key * a.k + col);
+}
+template <class A>
+__device__ __forceinline__ PVal load_w(const A& a, uint32_t key) {
+  if constexpr (A::kLines) return pv_load(a.w, a.ws1, a.ws2, (size_t)key * a.rs, key);
+  else return pv_load(a.w, a.ws1, a.ws2, key);
+}
+template <class A>
+__device__ __forceinline__ void store_emb(const A& a, const PVal& v, uint32_t key, int col) {
+  if constexpr (A::kLines) pv_store(v, a.emb, a.es1, a.es2, (size_t)key * a.rs + col, (size_t)key * a.k + col);
+  else pv_store(v, a.emb, a.es1, a.es2, (size_t)key * a.k + col);
+}
+template <class A>
+__device__ __forceinline__ void store_w(const A& a, const PVal& v, uint32_t key) {
+  if constexpr (A::kLines) pv_store(v, a.w, a.ws1, a.ws2, (size_t)key * a.rs, key);
+  else pv_store(v, a.w, a.ws1, a.ws2, key);
+}
+
 // the row of id `key` from its loaded values: column col of the embedding (lanes with act) and, lane 0 of the
 // group, the weight; the line copy gets the new values too
-__device__ __forceinline__ void finish_row(const TabArgs& a, uint32_t key, int gl, int col, bool act, bool do_w,
+template <class A>
+__device__ __forceinline__ void finish_row(const A& a, uint32_t key, int gl, int col, bool act, bool do_w,
                                            PVal pe, PVal pw, float ge_sum, float gw_sum) {
   if (act) {
     pe.p = opt_update(a.h, pe.p, ge_sum, pe.s1, pe.s2);
-    pv_store(pe, a.emb, a.es1, a.es2, (size_t)key * a.k + col);
+    store_emb(a, pe, key, col);
     if (a.line) a.line[(size_t)key * 32 + col] = pe.p;
   }
   if (do_w && gl == 0) {
     pw.p = opt_update(a.h, pw.p, gw_sum, pw.s1, pw.s2);
-    pv_store(pw, a.w, a.ws1, a.ws2, key);
+    store_w(a, pw, key);
     if (a.line) a.line[(size_t)key * 32 + 16] = pw.p;
   }
 }
@@ -293,8 +338,8 @@ __device__ __forceinline__ void finish_row(const TabArgs& a, uint32_t key, int g
 // K16: the table has 16 columns, lane j of a group owns column j; else column chunks of 16 in turn.
 // Everything a group needs to place itself comes from one round of loads: its key, the key before, the 16 keys
 // after (one a lane) and the 16 nonzeros from its position on.
-template <bool K16>
-__global__ __launch_bounds__(256) void tab_update_kernel(TabArgs a) {
+template <bool K16, class A>
+__global__ __launch_bounds__(256) void tab_update_kernel(A a) {
   const size_t gp = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
   const int gl = threadIdx.x & 15;
   if (gp >= (size_t)a.n) return;
@@ -341,8 +386,8 @@ __global__ __launch_bounds__(256) void tab_update_kernel(TabArgs a) {
     const bool act = col < ke;
     const bool do_w = has_w && c == 0;
     PVal pe{}, pw{};  // the row's old values, in flight while the gradient rows are summed
-    if (direct && act) pe = pv_load(a.emb, a.es1, a.es2, (size_t)key * a.k + col);
-    if (direct && do_w) pw = pv_load(a.w, a.ws1, a.ws2, key);
+    if (direct && act) pe = load_emb(a, key, col);
+    if (direct && do_w) pw = load_w(a, key);
     float se, sw;
     sum_list(a, p, cnt, gl, sv16, col, act, do_w, se, sw);
     if (direct) {
@@ -356,8 +401,8 @@ __global__ __launch_bounds__(256) void tab_update_kernel(TabArgs a) {
 }
 
 // lists longer than 512: the chunk sums added in chunk order, then the update; one group per 512-window
-template <bool K16>
-__global__ __launch_bounds__(256) void tab_long_kernel(TabArgs a, int windows) {
+template <bool K16, class A>
+__global__ __launch_bounds__(256) void tab_long_kernel(A a, int windows) {
   const int win = (int)((blockIdx.x * (unsigned)blockDim.x + threadIdx.x) >> 4);
   const int gl = threadIdx.x & 15;
   if (win >= windows) return;
@@ -380,8 +425,8 @@ __global__ __launch_bounds__(256) void tab_long_kernel(TabArgs a, int windows) {
       if (do_w) sw += r[a.k];
     }
     PVal pe{}, pw{};
-    if (act) pe = pv_load(a.emb, a.es1, a.es2, (size_t)key * a.k + col);
-    if (do_w) pw = pv_load(a.w, a.ws1, a.ws2, key);
+    if (act) pe = load_emb(a, key, col);
+    if (do_w) pw = load_w(a, key);
     finish_row(a, key, gl, col, act, do_w, pe, pw, se, sw);
   }
 }
@@ -475,7 +520,7 @@ int ensure_scratch(rmx_optim& o, int64_t nnz) {
   }
   if (!st) st = o.hist.alloc(tiles * kRsBins, "rmx_optim", kMinElems);
   if (!st) st = o.bsum.alloc(tiles * kRsBins / kScanBlock + 1, "rmx_optim", kMinElems);
-  if (!st) st = o.part.alloc(2 * windows * ((size_t)o.t->k + 1), "rmx_optim", kMinElems);
+  if (!st) st = o.part.alloc(2 * windows * ((size_t)o.k + 1), "rmx_optim", kMinElems);
   if (!st) st = o.long_head.alloc(windows, "rmx_optim", kMinElems);
   if (st) return st;
   o.cap_nnz = nnz;
@@ -516,17 +561,17 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int optim_alloc(rmx_optim& o) {
   const rmx_model& m = *o.m;
-  const rmx_table& t = *o.t;
+  const size_t rows = (size_t)o.rows * o.nparts;  // the table's V, or every partition held here
   RMX_HIP(hipSetDevice(m.ctx->device));
   int st = RMX_OK;
   for (int i = 0; i < o.nslots && !st; ++i) {
     if (o.upd_w) {
-      if ((st = o.w_s[i].alloc((size_t)t.V, "rmx_optim", kMinElems))) break;
-      RMX_HIP(hipMemsetAsync(o.w_s[i], 0, sizeof(float) * t.V, m.ctx->stream));
+      if ((st = o.w_s[i].alloc(rows, "rmx_optim", kMinElems))) break;
+      RMX_HIP(hipMemsetAsync(o.w_s[i], 0, sizeof(float) * rows, m.ctx->stream));
     }
-    if (o.upd_e && t.k > 0) {
-      if ((st = o.e_s[i].alloc((size_t)t.V * t.k, "rmx_optim", kMinElems))) break;
-      RMX_HIP(hipMemsetAsync(o.e_s[i], 0, sizeof(float) * t.V * t.k, m.ctx->stream));
+    if (o.upd_e && o.k > 0) {
+      if ((st = o.e_s[i].alloc(rows * o.k, "rmx_optim", kMinElems))) break;
+      RMX_HIP(hipMemsetAsync(o.e_s[i], 0, sizeof(float) * rows * o.k, m.ctx->stream));
     }
     if (m.mats_len > 0) {
       if ((st = o.m_s[i].alloc((size_t)m.mats_len, "rmx_optim", kMinElems))) break;
@@ -562,7 +607,7 @@ int optim_ensure_grads(rmx_optim& o, int64_t nnz) {
   o.g_e.reset();
   o.g_nnz = 0;
   if (o.upd_w) st = o.g_w.alloc((size_t)nnz, "rmx_optim", kMinElems);
-  if (!st && o.upd_e) st = o.g_e.alloc((size_t)nnz * std::max(o.t->k, 1), "rmx_optim", kMinElems);
+  if (!st && o.upd_e) st = o.g_e.alloc((size_t)nnz * std::max(o.k, 1), "rmx_optim", kMinElems);
   if (st) return st;
   o.g_nnz = nnz;
   return RMX_OK;
@@ -574,14 +619,34 @@ static bool optim_host_values(const rmx_optim& o, bool bias, bool mats) {
   return bias || (mats && (m.has_bo || (m.type == RMX_MODEL_DCN && m.cross_depth <= kMaxFusedCross)));
 }
 
-int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias, const float* g_w,
-                const float* g_emb, const float* g_mats, const float* loss_dev, float* loss, bool sync) {
-  rmx_model& m = *o.m;
-  rmx_table& t = *o.t;
-  if (!o.upd_w) g_w = nullptr;
-  if (!o.upd_e || t.k <= 0) g_emb = nullptr;
-  if (m.mats_len <= 0) g_mats = nullptr;
-  const int64_t nnz = (int64_t)B * m.F;
+__global__ __launch_bounds__(256) void plane_sum_kernel(int N, int64_t len, const float* __restrict__ planes,
+                                                       float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= len) return;
+  float v = planes[i];
+  for (int r = 1; r < N; ++r) v += planes[(int64_t)r * len + i];
+  out[i] = v;
+}
+
+int optim_sum_planes(hipStream_t s, int N, int64_t len, const float* planes, float* out) {
+  if (len <= 0) return RMX_OK;
+  hipLaunchKernelGGL(plane_sum_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, N, len, planes, out);
+  RMX_HIP(hipGetLastError());
+  return RMX_OK;
+}
+
+int optim_bucket_sort(rmx_optim& o, hipStream_t s, int64_t n, const int32_t* keys, int nkeys) {
+  if (n <= 0) return RMX_OK;
+  if (nkeys >= kRsBins || n >= (int64_t(1) << 31) - kRsTile) {
+    set_error("rmx_optim_apply: batch * nFields must fit int32");
+    return RMX_E_INVALID;
+  }
+  if (int st = ensure_scratch(o, n)) return st;
+  return sort_pass<true>(s, keys, nullptr, nullptr, o.keys[0], o.vals[0], o.hist, o.bsum, (int)n, 0, (uint32_t)nkeys);
+}
+
+int optim_sparse_update(rmx_optim& o, hipStream_t s, int64_t nnz, const int32_t* ids, const SparseRows& t,
+                        const float* g_w, const float* g_emb) {
   if (nnz >= (int64_t(1) << 31) - kRsTile) {
     set_error("rmx_optim_apply: batch * nFields must fit int32");
     return RMX_E_INVALID;
@@ -605,7 +670,7 @@ int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, cons
     }
     const int windows = n / kChunkRows + 1;
     RMX_HIP(hipMemsetAsync(o.long_head, 0xFF, sizeof(int32_t) * windows, s));
-    TabArgs a{};
+    LineArgs a{};
     a.sk = o.keys[cur];
     a.sv = o.vals[cur];
     a.n = n;
@@ -613,26 +678,44 @@ int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, cons
     a.k = t.k;
     a.gw = g_w;
     a.ge = g_emb;
-    a.w = (float*)t.w.get();
-    a.emb = (float*)t.emb.get();
+    a.w = t.w;
+    a.emb = t.emb;
+    a.rs = t.rs;
     a.line = t.line;
-    a.ws1 = o.w_s[0];
-    a.ws2 = o.w_s[1];
-    a.es1 = o.e_s[0];
-    a.es2 = o.e_s[1];
+    a.ws1 = t.ws[0];
+    a.ws2 = t.ws[1];
+    a.es1 = t.es[0];
+    a.es2 = t.es[1];
     a.part = o.part;
     a.long_head = o.long_head;
     a.h = h;
     const unsigned gA = (unsigned)(((int64_t)n * 16 + 255) / 256), gB = (unsigned)(((int64_t)windows * 16 + 255) / 256);
-    if (t.k == 16) {
-      hipLaunchKernelGGL(tab_update_kernel<true>, dim3(gA), dim3(256), 0, s, a);
-      hipLaunchKernelGGL(tab_long_kernel<true>, dim3(gB), dim3(256), 0, s, a, windows);
+    if (t.rs > 0) {  // a shard partition's line rows
+      if (t.k == 16) {
+        hipLaunchKernelGGL((tab_update_kernel<true, LineArgs>), dim3(gA), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((tab_long_kernel<true, LineArgs>), dim3(gB), dim3(256), 0, s, a, windows);
+      } else {
+        hipLaunchKernelGGL((tab_update_kernel<false, LineArgs>), dim3(gA), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((tab_long_kernel<false, LineArgs>), dim3(gB), dim3(256), 0, s, a, windows);
+      }
+    } else if (t.k == 16) {
+      hipLaunchKernelGGL((tab_update_kernel<true, TabArgs>), dim3(gA), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((tab_long_kernel<true, TabArgs>), dim3(gB), dim3(256), 0, s, a, windows);
     } else {
-      hipLaunchKernelGGL(tab_update_kernel<false>, dim3(gA), dim3(256), 0, s, a);
-      hipLaunchKernelGGL(tab_long_kernel<false>, dim3(gB), dim3(256), 0, s, a, windows);
+      hipLaunchKernelGGL((tab_update_kernel<false, TabArgs>), dim3(gA), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((tab_long_kernel<false, TabArgs>), dim3(gB), dim3(256), 0, s, a, windows);
     }
     RMX_HIP(hipGetLastError());
   }
+  return RMX_OK;
+}
+
+int optim_dense_update(rmx_optim& o, hipStream_t s, const float* g_bias, const float* g_mats, const float* loss_dev,
+                       float* loss, bool sync) {
+  rmx_model& m = *o.m;
+  if (m.mats_len <= 0) g_mats = nullptr;
+  const Hyper h = make_hyper(o, o.steps + 1);
+  int st;
   if (g_mats) {
     const int64_t n = m.mats_len;
     if (aligned16(g_mats)) {
@@ -683,6 +766,25 @@ int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, cons
   }
   if (loss) *loss = host[kOptimHostVals - 1];
   return RMX_OK;
+}
+
+int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias, const float* g_w,
+                const float* g_emb, const float* g_mats, const float* loss_dev, float* loss, bool sync) {
+  rmx_table& t = *o.t;
+  if (!o.upd_w) g_w = nullptr;
+  if (!o.upd_e || t.k <= 0) g_emb = nullptr;
+  SparseRows r;
+  r.V = t.V;
+  r.k = t.k;
+  r.w = (float*)t.w.get();
+  r.emb = (float*)t.emb.get();
+  r.line = t.line;
+  for (int i = 0; i < 2; ++i) {
+    r.ws[i] = o.w_s[i];
+    r.es[i] = o.e_s[i];
+  }
+  if (int st = optim_sparse_update(o, s, (int64_t)B * o.m->F, ids, r, g_w, g_emb)) return st;
+  return optim_dense_update(o, s, g_bias, g_mats, loss_dev, loss, sync);
 }
 
 }  // namespace rmx

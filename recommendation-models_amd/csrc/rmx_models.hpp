@@ -169,9 +169,16 @@ struct rmx_model {
 
 // Device-resident optimiser of one (model, table) pair (optim.hip): the state slots, the grouping scratch of
 // the sparse update and the gradient buffers of rmx_train_step_ids.  Used under its model's lock.
+// Or of a (model, shard) pair (rmx_optim_create_sharded; the push, shard.hip): t is null then, and the table
+// state slots hold one [rows][k] / [rows] block per partition held here (a loopback shard: nparts = N), used
+// under the shard's lock, then the model's.
 struct rmx_optim {
   rmx_model* m = nullptr;
   rmx_table* t = nullptr;
+  rmx_shard* sh = nullptr;
+  int k = 0;                       // columns of the table / shard
+  int64_t rows = 0;                // rows a state block covers: the table's V, a partition's rows_per
+  int nparts = 1;
   int kind = 0;
   double eta = 0, a = 0, b = 0, eps = 0;  // a: momentum / factor / beta; b: gamma (Adam)
   int64_t steps = 0;
@@ -193,6 +200,18 @@ struct rmx_optim {
   // rmx_train_step_ids' gradients
   int64_t g_nnz = 0;
   rmx::DevBuf<float> g_b, g_w, g_e, g_m;  // g_b: [2] = {g_bias, loss}
+  // the push of a sharded optimiser (shard.hip), grown on demand after a device synchronise
+  int64_t cap_push = 0;                 // nonzeros the bucketing buffers hold
+  rmx::DevBuf<int32_t> p_key;           // [nnz] owner of nonzero n (N: its id is outside the table)
+  rmx::DevBuf<int32_t> p_loc;           // [nnz] its row there
+  rmx::DevBuf<int32_t> p_rows;          // [nnz] local rows, bucketed by owner, ascending nonzero inside a bucket
+  rmx::DevBuf<float> p_gw, p_ge;        // [nnz], [nnz][k] their gradient rows in that order
+  rmx::DevBuf<int32_t> p_cnt;           // [2N] bucket sizes sent | received
+  int64_t cap_pull = 0;                 // rows the owner-side list holds
+  rmx::DevBuf<int32_t> r_rows;          // [received] the buckets of every source rank in rank order (own at `rank`)
+  rmx::DevBuf<float> r_gw, r_ge;
+  rmx::DevBuf<float> d_rx;              // [N][mats_len + 1] every rank's {g_mats, g_bias}
+  rmx::DevBuf<float> d_sum;             // [mats_len + 1] their sum in rank order
 };
 
 namespace rmx {
@@ -205,6 +224,33 @@ void optim_release(rmx_optim& o);
 int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias, const float* g_w,
                 const float* g_emb, const float* g_mats, const float* loss_dev, float* loss, bool sync);
 int optim_ensure_grads(rmx_optim& o, int64_t nnz);  // rmx_train_step_ids' gradient buffers for nnz nonzeros
+// The two halves of optim_apply, for the sharded push (shard.hip).  Both read the step count o.steps + 1; the
+// dense half then counts the step.
+struct SparseRows {  // the rows a sparse update writes, with their state slots
+  int64_t V = 0;     // keys >= V are skipped
+  int k = 0;
+  float* w = nullptr;    // [V]; rs > 0: the w slot of row 0 (emb + k), stride rs
+  float* emb = nullptr;  // [V][k]; rs > 0: [V][rs] line rows [emb k | w | pad] of a shard partition
+  int rs = 0;
+  float* line = nullptr;  // a table's line copy (rs == 0 only)
+  float* ws[2] = {nullptr, nullptr};  // state, dense [V] / [V][k] either way
+  float* es[2] = {nullptr, nullptr};
+};
+int optim_sparse_update(rmx_optim& o, hipStream_t s, int64_t nnz, const int32_t* ids, const SparseRows& t,
+                        const float* g_w, const float* g_emb);
+int optim_dense_update(rmx_optim& o, hipStream_t s, const float* g_bias, const float* g_mats, const float* loss_dev,
+                       float* loss, bool sync);
+// One stable pass over keys[0, n): the positions grouped by key, ascending inside a key, into o.vals[0] and the
+// sorted keys into o.keys[0].  Keys outside [0, nkeys) count as nkeys (last); nkeys < 256.
+int optim_bucket_sort(rmx_optim& o, hipStream_t s, int64_t n, const int32_t* keys, int nkeys);
+// out[i] = planes[0][i] + planes[1][i] + ... in that order (fp32), planes [N][len]
+int optim_sum_planes(hipStream_t s, int N, int64_t len, const float* planes, float* out);
+// the argument checks and hyper-parameters shared by rmx_optim_create / rmx_optim_create_sharded (capi.hip): a new
+// optimiser for model m without its table or shard, or a status
+int optim_new(const char* who, rmx_model* m, int kind, const double* hyper, int n_hyper, rmx_optim** out);
+// the collective apply of a sharded optimiser (shard.hip; takes the shard's lock, then the model's)
+int shard_optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias,
+                      const float* g_w, const float* g_emb, const float* g_mats);
 int model_build(rmx_model& m);
 void model_init_mats(const rmx_model& m, uint64_t seed, float* mats);
 void model_release(rmx_model& m);

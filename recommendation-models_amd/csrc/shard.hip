@@ -1485,6 +1485,368 @@ int forward_direct(rmx_model& m, rmx_shard& sh, hipStream_t s, int B, const int3
   return model_forward(m, s, in);
 }
 
+// rmx_shard_pull under the shard's lock (ShardUse) held by the caller
+int shard_pull_locked(const char* who, rmx_shard& sh, hipStream_t s, int64_t n, const int32_t* d_ids, int slot) {
+  if (sh.slot_nnz[slot] >= 0) {
+    set_error(std::string(who) + ": slot " + std::to_string(slot) + " holds a pull no forward has consumed yet");
+    return RMX_E_INVALID;
+  }
+  for (int q = 0; q < 2; ++q)
+    if (!sh.ready[q]) {
+      RMX_HIP(hipEventCreateWithFlags(&sh.ready[q], hipEventDisableTiming));
+      RMX_HIP(hipEventCreateWithFlags(&sh.consumed[q], hipEventDisableTiming));
+    }
+  // the slot's previous forward must have read it before the exchange overwrites it
+  if (sh.consumed_rec[slot]) RMX_HIP(hipStreamWaitEvent(s, sh.consumed[slot], 0));
+  const bool direct = direct_eligible(sh);
+  int st = direct ? shard_map_rows(sh, s, n, d_ids, slot) : shard_exchange(sh, s, n, d_ids, slot);
+  if (st) return st;
+  sh.slot_direct[slot] = direct;
+  RMX_HIP(hipEventRecord(sh.ready[slot], s));
+  sh.slot_nnz[slot] = n;
+  return RMX_OK;
+}
+
+// The slot side of a call that consumes a pull (the shard's mutex held by the caller): the slot holds nnz ids,
+// its overflow check is done and stream s waits for the pull; slot_end marks the slot read and frees it.
+int slot_begin(const char* who, rmx_shard& sh, int slot, int64_t nnz, hipStream_t s) {
+  if (sh.slot_nnz[slot] != nnz) {
+    set_error(sh.slot_nnz[slot] < 0 ? std::string(who) + ": nothing pulled into slot " + std::to_string(slot)
+                                    : std::string(who) + ": the slot holds " + std::to_string(sh.slot_nnz[slot]) +
+                                          " ids, not batch * nFields");
+    return sh.slot_nnz[slot] < 0 ? RMX_E_INVALID : RMX_E_SHAPE;
+  }
+  if (int st = shard_resolve(sh, slot)) return st;
+  RMX_HIP(hipStreamWaitEvent(s, sh.ready[slot], 0));
+  return RMX_OK;
+}
+int slot_end(rmx_shard& sh, int slot, hipStream_t s) {
+  RMX_HIP(hipEventRecord(sh.consumed[slot], s));
+  sh.consumed_rec[slot] = true;
+  sh.slot_nnz[slot] = -1;
+  return RMX_OK;
+}
+
+// The training pass over the rows in pull slot `slot`: ids = the slot's row list, table = its rows.  The
+// backward takes no line rows, so a directly-mapped slot copies its rows out first (as forward_direct does for
+// the models that read no lines): owner gather through the mapped rows, then the identity list.
+int train_pulled(rmx_model& m, rmx_shard& sh, hipStream_t s, int B, int slot, const TrainOutputs& to) {
+  int32_t* perm = sh.perm_s[slot];
+  const int64_t n = (int64_t)B * m.F;
+  if (sh.slot_direct[slot] && n > 0) {
+    if (int st = launch_owner_gather(s, n, sh.k, sh.rs, perm, sh.part[0], sh.recv_emb_s[slot], sh.recv_w_s[slot]))
+      return st;
+    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, perm);
+    RMX_HIP(hipGetLastError());
+  }
+  FwdInputs in;
+  in.B = B;
+  in.ids = perm;
+  in.table = sh.recv_emb_s[slot];
+  in.wtab = sh.recv_w_s[slot];
+  in.dtype = kF32;
+  in.beta = m.beta;
+  return model_train(m, s, in, to);
+}
+
+// what rmx_forward_pulled checks of its model, in its order
+int pulled_model_checks(const char* who_c, const rmx_model* m, const rmx_shard* sh) {
+  const std::string who(who_c);
+  if (!m->params_ready && m->mats_len > 0) {
+    set_error(who + ": call rmx_model_set_mats first");
+    return RMX_E_INVALID;
+  }
+  if (!m->beta_set) {
+    set_error(who + ": call rmx_model_set_bias first");
+    return RMX_E_INVALID;
+  }
+  if (m->precision != RMX_DTYPE_F32) {
+    set_error(who + ": sharded tables are fp32 (model precision must be RMX_DTYPE_F32)");
+    return RMX_E_INVALID;
+  }
+  if (m->type != RMX_MODEL_LR && sh->k != m->k) {
+    set_error(who + ": table embedding_dim differs from the model's");
+    return RMX_E_SHAPE;
+  }
+  return RMX_OK;
+}
+
+// ------------------------------------------------------------------ the push ----
+// The optimiser step on a shard (include/rmx.h "sharded optimiser"): every rank's per-nonzero
+// gradients go to the owners of their ids, and each owner runs the replicated table's sort / ordered sum / update
+// (optim.hip) over what it received, laid out in ascending (source rank, nonzero) order -- the order of the
+// ranks' batches concatenated, so the sums are those of rmx_optim_apply on a replicated table, bit for bit.
+//   1. bucket : owner and local row of every nonzero, one stable radix pass keyed by the owner (optim.hip's
+//               rs_* kernels; ids outside [0, V) take key N and are dropped), then one pack kernel writes each
+//               bucket's local rows and gradient rows contiguously.  (The pull's route kernels reserve their
+//               bucket ranges with atomics: their in-bucket order is arbitrary, fine for copies, not for sums.)
+//   2. counts : one int to every peer -- with every rank's g_mats and g_bias in the same grouped step -- then
+//               one D2H of the 2N counts (a host sync: the transport needs host-side message sizes).
+//   3. rows   : local rows, g_w and g_emb rows to each owner; the own bucket is a device copy; a zero count
+//               sends nothing.
+//   4. update : the sort by local row, the per-list ordered sum and the update against the partition's
+//               [emb | w | pad] rows (optim_sparse_update, SparseRows::rs).
+//   5. dense  : the N {g_mats, g_bias} planes added in rank order, then the elementwise update and the repack:
+//               every rank computes the same bits, so the replicas stay identical without a broadcast.
+// A loopback shard runs 1 and 4 per partition on one stream; one rank has no exchange at all (and no sync).
+
+// owner and local row of every nonzero's id (key N: no owner)
+__global__ __launch_bounds__(256) void push_key_kernel(int64_t n, int N, const int32_t* __restrict__ ids,
+                                                      int32_t* __restrict__ key, int32_t* __restrict__ loc,
+                                                      OwnerPerm op) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int l = 0;
+  const int o = route_owner(ids, i, n, N, &l, op);
+  key[i] = o < 0 ? N : o;
+  loc[i] = l;
+}
+
+// cnt[o] = the sorted keys equal to o (two lower bounds)
+__global__ void push_count_kernel(int n, int N, const uint32_t* __restrict__ sk, int32_t* __restrict__ cnt) {
+  const int o = threadIdx.x;
+  if (o >= N) return;
+  int b[2];
+  for (int i = 0; i < 2; ++i) {
+    const uint32_t key = (uint32_t)(o + i);
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sk[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    b[i] = lo;
+  }
+  cnt[o] = b[1] - b[0];
+}
+
+// position q of the owner-sorted list holds nonzero sv[q]: its local row and gradient rows, bucket after bucket
+__global__ __launch_bounds__(256) void push_pack_kernel(int64_t n, int N, int k, const uint32_t* __restrict__ sk,
+                                                       const uint32_t* __restrict__ sv,
+                                                       const int32_t* __restrict__ loc, const float* __restrict__ gw,
+                                                       const float* __restrict__ ge, int32_t* __restrict__ rows,
+                                                       float* __restrict__ ogw, float* __restrict__ oge) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int kk = max(k, 1);
+  const int64_t q = t / kk;
+  const int j = (int)(t - q * kk);
+  if (q >= n || sk[q] >= (uint32_t)N) return;  // (the dropped ids sort last)
+  const uint32_t nz = sv[q];
+  if (ge && j < k) oge[q * k + j] = ge[(int64_t)nz * k + j];
+  if (j == 0) {
+    rows[q] = loc[nz];
+    if (gw) ogw[q] = gw[nz];
+  }
+}
+
+int ensure_push(rmx_optim& o, int64_t nnz) {
+  if (nnz <= o.cap_push) return RMX_OK;
+  RMX_HIP(hipDeviceSynchronize());  // a peer's copy out of the old buffers may still be in flight
+  o.cap_push = 0;
+  int st;
+  if ((st = o.p_key.alloc(nnz, "rmx_optim")) || (st = o.p_loc.alloc(nnz, "rmx_optim")) ||
+      (st = o.p_rows.alloc(nnz, "rmx_optim")) || (o.upd_w && (st = o.p_gw.alloc(nnz, "rmx_optim"))) ||
+      (o.upd_e && (st = o.p_ge.alloc(nnz * std::max(o.k, 1), "rmx_optim"))))
+    return st;
+  o.cap_push = nnz;
+  return RMX_OK;
+}
+
+int ensure_pushed(rmx_optim& o, int64_t n) {  // the owner side
+  if (n <= o.cap_pull) return RMX_OK;
+  RMX_HIP(hipDeviceSynchronize());
+  o.cap_pull = 0;
+  int st;
+  if ((st = o.r_rows.alloc(n, "rmx_optim")) || (o.upd_w && (st = o.r_gw.alloc(n, "rmx_optim"))) ||
+      (o.upd_e && (st = o.r_ge.alloc(n * std::max(o.k, 1), "rmx_optim"))))
+    return st;
+  o.cap_pull = n;
+  return RMX_OK;
+}
+
+SparseRows partition_rows(const rmx_optim& o, int part) {
+  const rmx_shard& sh = *o.sh;
+  SparseRows r;
+  r.V = sh.rows_per;
+  r.k = sh.k;
+  r.emb = sh.part[part];
+  r.w = sh.part[part] + sh.k;
+  r.rs = sh.rs;
+  for (int i = 0; i < 2; ++i) {
+    r.ws[i] = o.w_s[i] ? o.w_s[i] + (size_t)part * o.rows : nullptr;
+    r.es[i] = o.e_s[i] ? o.e_s[i] + (size_t)part * o.rows * o.k : nullptr;
+  }
+  return r;
+}
+
+// One step of a sharded optimiser; the caller holds the shard's lock and the model's.  Collective at N > 1.
+int shard_push(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias, const float* g_w,
+               const float* g_emb, const float* g_mats, const float* loss_dev, float* loss, bool sync) {
+  rmx_shard& sh = *o.sh;
+  rmx_model& m = *o.m;
+  const int N = sh.N, k = sh.k, me = sh.rank;
+  if (!o.upd_w) g_w = nullptr;
+  if (!o.upd_e) g_emb = nullptr;
+  if (m.mats_len <= 0) g_mats = nullptr;
+  const int64_t nnz = (int64_t)B * m.F, kLimit = (int64_t(1) << 31) - 4096;
+  const bool sparse = g_w || g_emb;
+  if (nnz >= kLimit) {
+    set_error("rmx_optim_apply: batch * nFields must fit int32");
+    return RMX_E_INVALID;
+  }
+  const OwnerPerm op = owner_perm_of(sh);
+  int st;
+  if (N == 1) {  // no exchange, no host sync: the rows of the batch's ids (rows_per: outside the table, skipped)
+    if (sparse && nnz > 0) {
+      if ((st = ensure_push(o, nnz))) return st;
+      hipLaunchKernelGGL(own_rows_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, nnz, ids,
+                         (int32_t)sh.rows_per, o.p_rows, op);
+      RMX_HIP(hipGetLastError());
+      if ((st = optim_sparse_update(o, s, nnz, o.p_rows, partition_rows(o, 0), g_w, g_emb))) return st;
+    }
+    return optim_dense_update(o, s, g_bias, g_mats, loss_dev, loss, sync);
+  }
+  const bool xch = !sh.loopback;
+  if (xch && sh.failed) {
+    set_error("rmx_optim_apply: an earlier exchange failed on this rank, so its collectives no longer pair up "
+              "with its peers'; abort the shard (rmx_shard_abort) and create a new one");
+    return RMX_E_COMM;
+  }
+  if (xch && sh.comm_state.load() != 0) {
+    set_error("rmx_optim_apply: the communicator was aborted (rmx_shard_abort)");
+    return RMX_E_COMM;
+  }
+  // From here every rank passes both start() / end() brackets, also after a local error (shard_exchange).
+  int err = RMX_OK;
+  auto keep = [&](int e) {
+    if (e && err == RMX_OK) err = e;
+    return err == RMX_OK;
+  };
+  auto hip_ok = [&](hipError_t e) {
+    if (e != hipSuccess) {
+      set_error(std::string("rmx_optim_apply: HIP error ") + hipGetErrorString(e));
+      return (int)RMX_E_HIP;
+    }
+    return (int)RMX_OK;
+  };
+  int32_t* cnt = o.p_cnt;       // [N] bucket sizes
+  int32_t* rcnt = o.p_cnt + N;  // [N] received
+  // 1. stable bucketing by owner
+  keep(hip_ok(hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * N, s)));
+  if (sparse && nnz > 0) {
+    if (keep(ensure_push(o, nnz))) {
+      hipLaunchKernelGGL(push_key_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, nnz, N, ids, o.p_key,
+                         o.p_loc, op);
+      keep(hip_ok(hipGetLastError()));
+    }
+    if (err == RMX_OK && keep(optim_bucket_sort(o, s, nnz, o.p_key, N))) {
+      hipLaunchKernelGGL(push_count_kernel, dim3(1), dim3(kMaxRanks), 0, s, (int)nnz, N, o.keys[0], cnt);
+      const int kp = g_emb ? k : 0;
+      const int64_t threads = nnz * std::max(kp, 1);
+      hipLaunchKernelGGL(push_pack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, nnz, N, kp,
+                         o.keys[0].get(), o.vals[0].get(), o.p_loc.get(), g_w, g_emb, o.p_rows.get(), o.p_gw.get(),
+                         o.p_ge.get());
+      keep(hip_ok(hipGetLastError()));
+    }
+  }
+  int32_t* hc = sh.h_counts;
+  int32_t* hr = sh.h_counts + N;
+  if (!xch) {
+    // loopback: partition p takes bucket p in place
+    if (err) return err;
+    RMX_HIP(hipMemcpyAsync(hc, cnt, sizeof(int32_t) * N, hipMemcpyDeviceToHost, s));
+    RMX_HIP(hipStreamSynchronize(s));
+    for (int64_t p = 0, off = 0; p < N; off += hc[p], ++p)
+      if (hc[p] > 0 && (st = optim_sparse_update(o, s, hc[p], o.p_rows + off, partition_rows(o, (int)p),
+                                                 g_w ? o.p_gw + off : nullptr, g_emb ? o.p_ge + off * k : nullptr)))
+        return st;
+    return optim_dense_update(o, s, g_bias, g_mats, loss_dev, loss, sync);
+  }
+  Transport& tr = *sh.tr;
+  const int64_t L = m.mats_len + 1;
+  float* rx = o.d_rx;  // [N][L]
+  // 2. counts, and every rank's dense gradients, to every peer
+  keep(tr.start());
+  for (int p = 0; p < N && err == RMX_OK; ++p) {
+    if (p == me) continue;
+    if (sparse && keep(tr.send(cnt + p, sizeof(int32_t), p, s))) keep(tr.recv(rcnt + p, sizeof(int32_t), p, s));
+    if (g_mats && err == RMX_OK && keep(tr.send(g_mats, sizeof(float) * m.mats_len, p, s)))
+      keep(tr.recv(rx + p * L, sizeof(float) * m.mats_len, p, s));
+    if (g_bias && err == RMX_OK && keep(tr.send(g_bias, sizeof(float), p, s)))
+      keep(tr.recv(rx + p * L + m.mats_len, sizeof(float), p, s));
+  }
+  keep(tr.end(s));
+  if (err == RMX_OK && sparse) {
+    if (hipMemcpyAsync(sh.h_counts, cnt, sizeof(int32_t) * 2 * N, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+      set_error("rmx_optim_apply: the counts' device-to-host copy failed");
+      keep(RMX_E_HIP);
+    }
+  }
+  if (err == RMX_OK && sh.comm_state.load() != 0) {
+    set_error("rmx_optim_apply: the communicator was aborted (rmx_shard_abort)");
+    keep(RMX_E_COMM);
+  }
+  if (err != RMX_OK || !sparse) std::fill(sh.h_counts, sh.h_counts + 2 * N, 0);  // post nothing from here
+  hr[me] = hc[me];
+  // The owner's list: the buckets of source ranks 0 .. N-1 in that order, this rank's own at position `rank`.
+  std::vector<int64_t> so(N + 1, 0), ro(N + 1, 0);
+  for (int p = 0; p < N; ++p) {
+    so[p + 1] = so[p] + hc[p];
+    ro[p + 1] = ro[p] + hr[p];
+  }
+  const int64_t total = ro[N];
+  if (err == RMX_OK && total >= kLimit) {
+    set_error("rmx_optim_apply: the nonzeros pushed to this rank must fit int32");
+    keep(RMX_E_INVALID);
+  }
+  if (err == RMX_OK) keep(ensure_pushed(o, total));
+  // 3. rows to owners
+  keep(tr.start());
+  for (int p = 0; p < N && err == RMX_OK; ++p) {
+    if (p == me) continue;
+    if (hc[p]) {
+      keep(tr.send(o.p_rows + so[p], sizeof(int32_t) * hc[p], p, s));
+      if (g_w && err == RMX_OK) keep(tr.send(o.p_gw + so[p], sizeof(float) * hc[p], p, s));
+      if (g_emb && err == RMX_OK) keep(tr.send(o.p_ge + so[p] * k, sizeof(float) * hc[p] * k, p, s));
+    }
+    if (hr[p] && err == RMX_OK) {
+      keep(tr.recv(o.r_rows + ro[p], sizeof(int32_t) * hr[p], p, s));
+      if (g_w && err == RMX_OK) keep(tr.recv(o.r_gw + ro[p], sizeof(float) * hr[p], p, s));
+      if (g_emb && err == RMX_OK) keep(tr.recv(o.r_ge + ro[p] * k, sizeof(float) * hr[p] * k, p, s));
+    }
+  }
+  keep(tr.end(s));
+  if (err != RMX_OK) {
+    sh.failed = true;  // out of step with the peers (include/rmx.h)
+    return err;
+  }
+  if (hc[me]) {  // the own bucket stays local
+    const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
+    RMX_HIP(hipMemcpyAsync(o.r_rows + ro[me], o.p_rows + so[me], sizeof(int32_t) * hc[me], dd, s));
+    if (g_w) RMX_HIP(hipMemcpyAsync(o.r_gw + ro[me], o.p_gw + so[me], sizeof(float) * hc[me], dd, s));
+    if (g_emb) RMX_HIP(hipMemcpyAsync(o.r_ge + ro[me] * k, o.p_ge + so[me] * k, sizeof(float) * hc[me] * k, dd, s));
+  }
+  // 4. owner update
+  if (total > 0 && (st = optim_sparse_update(o, s, total, o.r_rows, partition_rows(o, 0), g_w ? o.r_gw.get() : nullptr,
+                                             g_emb ? o.r_ge.get() : nullptr)))
+    return st;
+  // 5. dense part: the planes added in rank order
+  if (g_mats) RMX_HIP(hipMemcpyAsync(rx + me * L, g_mats, sizeof(float) * m.mats_len, hipMemcpyDeviceToDevice, s));
+  if (g_bias) RMX_HIP(hipMemcpyAsync(rx + me * L + m.mats_len, g_bias, sizeof(float), hipMemcpyDeviceToDevice, s));
+  if ((g_mats || g_bias) && (st = optim_sum_planes(s, N, L, rx, o.d_sum))) return st;
+  return optim_dense_update(o, s, g_bias ? o.d_sum + m.mats_len : nullptr, g_mats ? o.d_sum.get() : nullptr, loss_dev,
+                            loss, sync);
+}
+
+int shard_optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, const float* g_bias,
+                      const float* g_w, const float* g_emb, const float* g_mats) {
+  ShardUse suse(*o.sh, s);  // lock order: shard, then model
+  if (suse.st) return suse.st;
+  ModelUse use(*o.m, s);
+  if (use.st) return use.st;
+  return shard_push(o, s, B, ids, g_bias, g_w, g_emb, g_mats, nullptr, nullptr, false);
+}
+
 }  // namespace rmx
 
 // ------------------------------------------------------------------ C ABI --
@@ -1692,24 +2054,111 @@ extern "C" int rmx_shard_pull(rmx_shard* sh, int64_t n, const int32_t* d_ids, in
   hipStream_t s = stream ? (hipStream_t)stream : sh->ctx->stream;
   ShardUse use(*sh, s);  // the exchange's internal buffers: one pull at a time
   if (use.st) return use.st;
-  if (sh->slot_nnz[slot] >= 0) {
-    set_error("rmx_shard_pull: slot " + std::to_string(slot) + " holds a pull no forward has consumed yet");
+  return shard_pull_locked("rmx_shard_pull", *sh, s, n, d_ids, slot);
+}
+
+extern "C" int rmx_backward_pulled(rmx_model* m, rmx_shard* sh, int32_t B, int slot, const float* d_targets,
+                                   float* d_g_bias, float* d_g_weights, float* d_g_embedding, float* d_g_mats,
+                                   float* d_loss, void* stream) {
+  if (!m || !sh || B < 0 || (!d_targets && B > 0) || slot < 0 || slot > 1 || !m->ctx) {
+    set_error("rmx_backward_pulled: bad args (slot must be 0 or 1)");
     return RMX_E_INVALID;
   }
-  for (int q = 0; q < 2; ++q)
-    if (!sh->ready[q]) {
-      RMX_HIP(hipEventCreateWithFlags(&sh->ready[q], hipEventDisableTiming));
-      RMX_HIP(hipEventCreateWithFlags(&sh->consumed[q], hipEventDisableTiming));
-    }
-  // the slot's previous forward must have read it before the exchange overwrites it
-  if (sh->consumed_rec[slot]) RMX_HIP(hipStreamWaitEvent(s, sh->consumed[slot], 0));
-  const bool direct = direct_eligible(*sh);
-  int st = direct ? shard_map_rows(*sh, s, n, d_ids, slot) : shard_exchange(*sh, s, n, d_ids, slot);
+  int st = pulled_model_checks("rmx_backward_pulled", m, sh);
   if (st) return st;
-  sh->slot_direct[slot] = direct;
-  RMX_HIP(hipEventRecord(sh->ready[slot], s));
-  sh->slot_nnz[slot] = n;
+  RMX_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : m->ctx->stream;
+  {
+    std::lock_guard<std::mutex> lk(sh->mu);
+    if ((st = slot_begin("rmx_backward_pulled", *sh, slot, (int64_t)B * m->F, s))) return st;
+  }
+  {
+    ModelUse use(*m, s);
+    if (use.st) return use.st;
+    TrainOutputs to;
+    to.targets = d_targets;
+    to.nnz = (int64_t)B * m->F;
+    to.g_bias = d_g_bias;
+    to.g_w = d_g_weights;
+    to.g_emb = m->type == RMX_MODEL_LR ? nullptr : d_g_embedding;
+    to.g_mats = d_g_mats;
+    to.loss = d_loss;
+    st = train_pulled(*m, *sh, s, B, slot, to);
+  }
+  std::lock_guard<std::mutex> lk(sh->mu);
+  const int est = slot_end(*sh, slot, s);
+  return st ? st : est;
+}
+
+extern "C" int rmx_optim_create_sharded(rmx_model* m, rmx_shard* sh, int kind, const double* hyper, int n_hyper,
+                                        rmx_optim** out) {
+  const char* who = "rmx_optim_create_sharded";
+  rmx_optim* raw = nullptr;
+  int st = optim_new(who, m, kind, hyper, n_hyper, out ? &raw : nullptr);
+  if (st) return st;
+  std::unique_ptr<rmx_optim> o(raw);
+  if (!sh || m->precision != RMX_DTYPE_F32) {
+    set_error(std::string(who) + (sh ? ": fp32 models only" : ": shard is NULL"));
+    return RMX_E_INVALID;
+  }
+  if (m->type != RMX_MODEL_LR && sh->k != m->k) {
+    set_error(std::string(who) + ": shard embedding_dim " + std::to_string(sh->k) + " != model " + std::to_string(m->k));
+    return RMX_E_SHAPE;
+  }
+  o->sh = sh;
+  o->k = sh->k;
+  o->rows = sh->rows_per;
+  o->nparts = (int)sh->part.size();
+  if ((st = optim_alloc(*o)) || (st = o->p_cnt.alloc(2 * sh->N, who))) return st;
+  if (sh->N > 1 && !sh->loopback) {
+    const size_t L = (size_t)m->mats_len + 1;
+    if ((st = o->d_rx.alloc(L * sh->N, who)) || (st = o->d_sum.alloc(L, who))) return st;
+    RMX_HIP(hipMemset(o->d_rx, 0, sizeof(float) * L * sh->N));
+  }
+  *out = o.release();
   return RMX_OK;
+}
+
+extern "C" int rmx_train_step_sharded(rmx_model* m, rmx_shard* sh, rmx_optim* o, int32_t B, const int32_t* d_ids,
+                                      const float* d_targets, float* loss, void* stream) {
+  const char* who = "rmx_train_step_sharded";
+  if (!m || !sh || !o || B < 0 || ((!d_ids || !d_targets) && B > 0) || !m->ctx) {
+    set_error(std::string(who) + ": bad args");
+    return RMX_E_INVALID;
+  }
+  if (o->m != m || o->sh != sh) {
+    set_error(std::string(who) + (o->sh ? ": the optimiser belongs to another model / shard"
+                                        : ": the optimiser holds a table (rmx_train_step_ids)"));
+    return RMX_E_INVALID;
+  }
+  int st = pulled_model_checks(who, m, sh);
+  if (st) return st;
+  RMX_HIP(hipSetDevice(m->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : m->ctx->stream;
+  ShardUse suse(*sh, s);  // lock order: shard, then model
+  if (suse.st) return suse.st;
+  ModelUse use(*m, s);
+  if (use.st) return use.st;
+  if (sh->slot_nnz[0] >= 0) {
+    set_error(std::string(who) + ": pull slot 0 holds a pull no forward has consumed yet");
+    return RMX_E_INVALID;
+  }
+  const int64_t nnz = (int64_t)B * m->F;
+  if ((st = optim_ensure_grads(*o, nnz))) return st;
+  if ((st = shard_pull_locked(who, *sh, s, nnz, d_ids, 0))) return st;
+  if ((st = slot_begin(who, *sh, 0, nnz, s))) return st;
+  TrainOutputs to;
+  to.targets = d_targets;
+  to.nnz = nnz;
+  to.g_bias = o->g_b;
+  to.g_w = o->g_w;
+  to.g_emb = o->g_e;
+  to.g_mats = o->g_m;
+  to.loss = o->g_b + 1;
+  st = train_pulled(*m, *sh, s, B, 0, to);
+  const int est = slot_end(*sh, 0, s);
+  if (st || est) return st ? st : est;
+  return shard_push(*o, s, B, d_ids, o->g_b, o->g_w, o->g_e, o->g_m, o->g_b + 1, loss, true);
 }
 
 extern "C" int rmx_forward_pulled(rmx_model* m, rmx_shard* sh, int32_t B, int slot, float* d_out, void* stream) {

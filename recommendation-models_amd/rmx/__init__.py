@@ -660,6 +660,26 @@ class RecModel:
         """Forward over the rows ShardedTable.pull put in `slot` (waits for that pull on the device)."""
         check(_lib.lib.rmx_forward_pulled(self._device(), shard.handle, int(batch), int(slot), out_dev.ptr, stream))
 
+    def backward_pulled(self, shard, batch, slot, targets_dev, g_bias=None, g_weights=None, g_embedding=None,
+                        g_mats=None, loss=None, stream=None):
+        """Backward over the rows ShardedTable.pull put in `slot` (rmx_backward_pulled): backward_ids' outputs,
+        bit for bit those of a replicated table holding the same rows; consumes the slot."""
+        p = lambda a: None if a is None else a.ptr
+        check(_lib.lib.rmx_backward_pulled(self._device(), shard.handle, int(batch), int(slot), targets_dev.ptr,
+                                           p(g_bias), p(g_weights), p(g_embedding), p(g_mats), p(loss), stream))
+
+    def train_step_sharded(self, shard, optim, batch, ids_dev, targets_dev, stream=None):
+        """Collective: one training step over a ShardedTable (rmx_train_step_sharded) -- pull into slot 0,
+        backward into the optimiser's buffers, then its collective apply (the push).  Synchronous; returns this
+        rank's own mean BCE loss."""
+        if optim.model is not self or optim.shard is not shard:
+            raise IllegalArgumentError(_lib.RMX_E_INVALID, "train_step_sharded: the optimiser belongs to another "
+                                       "model / shard")
+        loss = ctypes.c_float()
+        check(_lib.lib.rmx_train_step_sharded(self._device(), shard.handle, optim.handle, int(batch), ids_dev.ptr,
+                                              targets_dev.ptr, ctypes.byref(loss), stream))
+        return loss.value
+
     def encoder_ids(self, table, batch, ids_dev, y_dev, stream=None):
         check(_lib.lib.rmx_encoder_ids(self._device(), table.handle, int(batch), ids_dev.ptr, y_dev.ptr, stream))
 
@@ -741,7 +761,10 @@ class Optimizer:
     gradients pushed through SGD / Momentum / Adagrad / Adam on the table rows, mats and the bias
     (ParRecModel.optimize, ParRecModel.scala:439-478; formulas and the summation order: include/rmx.h).
     kind: "sgd" (eta), "momentum" (eta, momentum=0.9), "adagrad" (eta, factor=0.9, eps=1e-7) or
-    "adam" (eta, gamma=0.99, beta=0.9, eps=1e-7), or the OPTIM_* number.  Keeps its model and table alive."""
+    "adam" (eta, gamma=0.99, beta=0.9, eps=1e-7), or the OPTIM_* number.  Keeps its model and table alive.
+    With a ShardedTable in the table's place (rmx_optim_create_sharded) apply() is COLLECTIVE -- the push: every
+    rank calls it for the same step with its own batch, and the step equals one apply on a replicated table over
+    the ranks' batches concatenated in rank order, bit for bit (gradients summed over the ranks, not averaged)."""
 
     KINDS = {"sgd": _lib.OPTIM_SGD, "momentum": _lib.OPTIM_MOMENTUM, "adagrad": _lib.OPTIM_ADAGRAD,
              "adam": _lib.OPTIM_ADAM}
@@ -765,12 +788,24 @@ class Optimizer:
         vals = [float(hyper.get(n, d)) for n, d in names[:last + 1]]
         arr = (ctypes.c_double * len(vals))(*vals)
         h = ctypes.c_void_p()
-        check(_lib.lib.rmx_optim_create(model._device(), table.handle, int(kind), arr, len(vals), ctypes.byref(h)))
+        sharded = isinstance(table, ShardedTable)
+        create = _lib.lib.rmx_optim_create_sharded if sharded else _lib.lib.rmx_optim_create
+        check(create(model._device(), table.handle, int(kind), arr, len(vals), ctypes.byref(h)))
         self.handle = h
         self.model = model
-        self.table = table
+        self.table = None if sharded else table
+        self.shard = table if sharded else None
         self.kind = int(kind)
         _track("optim", self)
+
+    def shard_state_ptrs(self, slot, part=0):
+        """(d_weights, d_embedding) device addresses (None where there is no such state) of state slot `slot` of
+        partition `part` of a sharded optimiser: [local rows] and [local rows][k] floats, indexed by the local row
+        of owner_hash (rmx_optim_shard_state_ptrs; part is 0 except on a loopback shard)."""
+        pw, pe = ctypes.c_void_p(), ctypes.c_void_p()
+        check(_lib.lib.rmx_optim_shard_state_ptrs(self.handle, int(part), int(slot), ctypes.byref(pw),
+                                                  ctypes.byref(pe)))
+        return pw.value, pe.value
 
     @property
     def steps(self):

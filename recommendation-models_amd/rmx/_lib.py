@@ -134,6 +134,10 @@ SIGNATURES = [
     ("rmx_forward_ids_sharded", c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     ("rmx_shard_pull", c_int, [c_vp, c_i64, c_vp, c_int, c_vp]),
     ("rmx_forward_pulled", c_int, [c_vp, c_vp, c_i32, c_int, c_vp, c_vp]),
+    ("rmx_backward_pulled", c_int, [c_vp, c_vp, c_i32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("rmx_optim_create_sharded", c_int, [c_vp, c_vp, c_int, P(ctypes.c_double), c_int, P(c_vp)]),
+    ("rmx_optim_shard_state_ptrs", c_int, [c_vp, c_int, c_int, P(c_vp), P(c_vp)]),
+    ("rmx_train_step_sharded", c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(c_f32), c_vp]),
 ]
 
 for _name, _res, _args in SIGNATURES:
