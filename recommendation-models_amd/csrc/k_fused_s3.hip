@@ -16,7 +16,26 @@
 // and p.
 //
 // Per row block (128 rows, a wave owns 16 of them and all 416 columns), one 3-slot weight ring, one barrier
-// per unit (one K step x one column half), unit U + 2's DMAs riding unit U's MFMAs:
+// per unit (one K step x one column half), validated ONE UNIT AHEAD:
+//   - a wave issues its five plane DMAs of unit U + 2 at tiles 0 .. 4 of unit U, into the slot of unit U - 1
+//     (every wave read it before the barrier at the head of U); every other vector-memory instruction of the
+//     unit comes after them (vmcnt retires in order);
+//   - the wait at the head of unit U + 1 leaves in flight only those other instructions -- 4 after a layer-1
+//     half-0 unit (1 id + 2 row + 1 weight DMA), 2 after layer 2's first unit (b2), otherwise 0 -- so the
+//     wave's planes of U + 2 have landed, and the barrier proves U + 2 for every wave (U + 1 was proven one
+//     barrier earlier; the prologue proves units 0 and 1);
+//   - so the weight-fragment prefetch does not stop at a unit's end: at its last tiles a wave reads the first
+//     fragments of the next unit (q_unit_ring, k_rowown.hpp), reaches the barrier with them in registers or
+//     in flight, and issues tile 0's MFMAs without a refill.  Before, the barrier at the head of U was what
+//     made U readable, and all eight waves left it with an empty fragment pipeline, 92 times per row block.
+//   The fragment registers rotate (tile t in register set (phase + t) mod (PF + 1)), and the phase per unit is
+//   a template argument: layers 2 and 3 are unrolled, so the ring is carried through layer 2's 26 units and
+//   through each half of layer 3; layer 1's loop is rolled and its 25-tile K step shifts the phase by one, so
+//   there the ring restarts at every half-0 unit (whose head forms the step's A operand after the barrier
+//   anyway) and is carried into the half-1 unit.  Nothing is carried across a layer boundary or a row block:
+//   23 restarts per row block at F = 39 instead of 92.
+//   The price: the planes' lead over their wait falls from ~1.5 units to one unit less the five-tile spread
+//   (they are L2 / Infinity-Cache resident).  Measured: DESIGN.md section 4, profiles/ring/.
 //   layer 1: 2 KS units -- (c, half 0) then (c, half 1), the A operand (two fields' gathered rows) split once
 //            per K step; ids three steps ahead and rows + first-order weights one step ahead (k_head_s3.hip),
 //            running on across row blocks: the next block's first rows land during this block's last steps
@@ -87,6 +106,38 @@ __device__ __forceinline__ void f_stamp(unsigned long long* dst, int lane, unsig
   do {                                                                                                   \
     if (blockIdx.x == 0 && (it) < kFDiagIt) f_stamp(&g_fused_t[w][it][ph], lane, __builtin_amdgcn_s_memtime()); \
   } while (0)
+// Inside one unit (row block 1 of block 0: layer 1's (kFProbeC1, half 0) and layer 2's (kFProbeC2, half 0)):
+// 0 before q_enter, 1 after its barrier, 2 at the issue of the first MFMA (tile 0's fragments landed), 3 after
+// the last MFMA.  Stores 0 .. 2 are older than the unit's plane DMAs, so the next q_enter's count still covers
+// what it must; store 3 makes that one wait stricter by one DMA (the unit after the probed one).
+constexpr int kFProbeC1 = 10, kFProbeC2 = 6;
+__device__ unsigned long long g_fused_r[kQW][2][4];  // [wave][layer 1 / layer 2][point]
+__device__ unsigned long long g_fused_rx[kQW];        // (the stamps of the units that are not probed)
+struct FProbe {
+  bool on;
+  int w, lane, kind;
+  template <int PEND>
+  __device__ __forceinline__ void at(int i) const {
+    // (no branch: a wave-uniform branch inside the unit made the compiler spill 88 VGPRs; every other unit of
+    // this place in the code stamps into a dummy word)
+    unsigned long long t;
+    asm volatile("s_waitcnt lgkmcnt(%1)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "n"(PEND) : "memory");
+    f_stamp(on ? &g_fused_r[w][kind][i] : &g_fused_rx[w], lane, t);
+  }
+};
+template <class L>
+struct FProbed {
+  using probe_tag = void;
+  const L& l;
+  const FProbe& pr;
+  __device__ __forceinline__ void operator()(int t) const { l(t); }
+  template <int PEND>
+  __device__ __forceinline__ void first() const {
+    pr.template at<PEND>(2);
+  }
+  __device__ __forceinline__ void last() const { pr.template at<15>(3); }
+};
+#define F_PROBE_AT(pr, i) (pr).template at<15>(i)
 #else
 #define F_STAMP(it, ph) \
   do {                  \
@@ -94,6 +145,19 @@ __device__ __forceinline__ void f_stamp(unsigned long long* dst, int lane, unsig
 #define F_USTAMP(it, u) \
   do {                  \
   } while (0)
+#define F_PROBE_AT(pr, i) \
+  do {                    \
+  } while (0)
+#endif
+// the extra functor of a probed unit: wrapped in diagnostic builds, itself otherwise
+#if RMX_FUSED_DIAG & 1
+#define F_PROBE_DECL(pr, cond, kind) const FProbe pr{(cond), w, lane, kind}
+#define F_PROBED(x, pr) FProbed<decltype(x)>{x, pr}
+#else
+#define F_PROBE_DECL(pr, cond, kind) \
+  do {                               \
+  } while (0)
+#define F_PROBED(x, pr) x
 #endif
 
 struct FusedS3Args {
@@ -112,7 +176,6 @@ struct FusedS3Args {
   const float* b3;
   OutArgs oa;             // wo [416], bo, beta, out
   int prio;
-  int dma_split;          // the two wave halves issue their DMAs at different tiles (knob "fused_dma_split")
 };
 
 // unit u of a row block -> its weight planes (wave-uniform)
@@ -259,9 +322,20 @@ __device__ __forceinline__ void f_b2_dma(const FusedS3Args& p, char* wl, int s, 
   lds_dma<16>(l < kQN / 4 - 64 ? p.b2 + 256 + 4 * l : zero16, dst + 1024);  // 1024 .. 1663, then zeros
 }
 
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression
+// (the fragment ring's phase per unit is a template argument of q_unit_ring)
+template <class F, int... I>
+__device__ __forceinline__ void f_static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void f_static_for(F&& f) {
+  f_static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
 // layer-3 half HF (column tiles 13 HF .. + 12; half 1 computes 12, tile 25 is padding): 13 units, one per
 // K step, unrolled so that h2's tiles 2c, 2c + 1 are static registers (k_tail_s3.hip q_layer3)
-template <int HF, int DOFF>
+template <int HF>
 __device__ __forceinline__ void f_layer3(const FusedS3Args& p, char* lds, const float* prm, f32x4 (&h2)[kQNT],
                                          int& slot, int w, int lane, int lo, int fb, float& part) {
   const int g = lane >> 4;
@@ -269,20 +343,23 @@ __device__ __forceinline__ void f_layer3(const FusedS3Args& p, char* lds, const 
 #pragma unroll
   for (int t = 0; t < kQUT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < kFKS2; ++c) {
-    q_enter<5>();
+  // the fragment ring is carried through the half's 13 units (each half starts its own: the output dot
+  // stands between them)
+  constexpr int NTU = HF == 0 ? kQUT : kQUT - 1;
+  f32x4 bq[RMX_FUSED_PF3 + 1][3];
+  f_static_for<kFKS2>([&](auto C) {
+    constexpr int c = decltype(C)::value;
+    q_enter<0>();
     bf16x8 ah, am, al;
-    split3(h2[2 * c], 2 * c + 1 < kQNT ? h2[2 * c + 1] : z, ah, am, al);
+    constexpr int c1 = 2 * c + 1 < kQNT ? 2 * c + 1 : 0;
+    split3(h2[2 * c], 2 * c + 1 < kQNT ? h2[c1] : z, ah, am, al);
     const int dslot = slot == 0 ? 2 : slot - 1;  // (slot + 2) mod 3
     const char* ub = lds + slot * kQUnit;
-    const bf16_t* src = f_src23(p, 2 * kFKS2 + HF * kFKS2 + c + 2);
-    if constexpr (HF == 0)
-      q_unit<kQUT, 0, kQUT, RMX_FUSED_PF3, kQN, DOFF>(ub, fb, ah, am, al, acc, src, lds, dslot, w, lo);
-    else
-      q_unit<kQUT - 1, 0, kQUT, RMX_FUSED_PF3, kQN, DOFF>(ub, fb, ah, am, al, acc, src, lds, dslot, w, lo);
     slot = q_next(slot);
-  }
+    const bf16_t* src = f_src23(p, 2 * kFKS2 + HF * kFKS2 + c + 2);
+    q_unit_ring<NTU, 0, kQUT, RMX_FUSED_PF3, (c * NTU) % (RMX_FUSED_PF3 + 1), c == 0, c + 1 < kFKS2>(
+        ub, lds + slot * kQUnit, fb, ah, am, al, acc, bq, src, lds, dslot, w, lo);
+  });
   // the output dot over this half's columns: ReLU(acc + b3)[n] * wo[n], n = 16 (13 HF + t) + 4 g + q
   constexpr int NT = HF == 0 ? kQUT : kQNT - kQUT;
   __builtin_amdgcn_sched_barrier(0);
@@ -355,41 +432,36 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
   __syncthreads();  // prm staged; this wave's units 0 and 1 landed (q_enter's barrier covers the rest)
 
   int slot = 0, s = 0;
-  // Round 6: the two waves of a SIMD (w and w + 4) issue their DMAs at different tiles of each unit -- the
-  // first half at tiles 0 .. 4 (and layer 1's gathers at 6 .. 11), the second half at tiles 6 .. 10 (gathers
-  // at 0 .. 3) -- so an LDS-DMA issue that holds one wave for ~100-200 cycles meets the partner's MFMAs
-  // instead of the partner's own DMA issue.  The vector-memory instructions per unit are the same, so every
-  // static vmcnt holds.  Each half runs its own copy of the loop (LATE is a compile-time flag; knob
-  // "fused_dma_split": 1 the second half late; 2 (default since late round 6) every wave late, i.e. layer 1's
-  // gathers at the head of each half-0 unit -- half a unit more lead on the row lines: configs[3]'s V = 100M
-  // partition +1.3 / +1.9 % on two boxes, V = 1M neutral, profiles/r06/ab_fused_dma2.txt; 0: every wave early).
-  const bool late = (w >= kQW / 2 && p.dma_split) || p.dma_split == 2;  // (2: every wave on the late tiles)
-  auto body = [&](auto LATE) {
-  constexpr bool kLate = decltype(LATE)::value != 0;
-  constexpr int kDoff = kLate ? 6 : 0;
+  // Every wave runs one schedule: the unit's five plane DMAs at tiles 0 .. 4, layer 1's id / row / weight DMAs at
+  // tiles 6, 8, 10, 11 of the half-0 unit, b2's at the last tile of layer 2's first unit -- the planes must be
+  // the oldest of the unit's vector-memory instructions (header: the static waits).  The knob "fused_dma_split"
+  // of rounds 5 / 6 (which wave half issued at which tiles) has no schedule of its own any more: 0, 1 and 2 are
+  // accepted and run this one.
   for (int it = 0; it < nit; ++it) {
     int row0, nw;
     p.rows.desc(blockIdx.x, it, row0, nw);
     if (w >= nw) {
-      // a half block's waves 4 .. 7: the same units, barriers and DMAs (ids of no rows), no MFMAs -- one
-      // branch per row block (per-unit branches spilled the accumulators)
+      // a half block's waves 4 .. 7: the same units, barriers and DMAs in the same order (ids of no rows), no
+      // fragment reads, no MFMAs -- one branch per row block (per-unit branches spilled the accumulators).
+      // (b2 is not DMA'd here, so the wait after layer 2's first unit is this wave's own count, 0)
 #pragma unroll 1
       for (int c = 0; c < KS; ++c, ++s) {
-        q_enter<5>();
+        q_enter<0>();
+        int dslot = slot == 0 ? 2 : slot - 1;
+        q_dma_only(f_ahead(p, 2 * c, 2), lds, dslot, w, lo);
+        __builtin_amdgcn_sched_barrier(0);
         id_dma(s + 3);
         f_row_dma(p, wl, s + 1, lane);
         __builtin_amdgcn_sched_barrier(0);
-        int dslot = slot == 0 ? 2 : slot - 1;
-        q_dma_only(f_ahead(p, 2 * c, 2), lds, dslot, w, lo);
         slot = q_next(slot);
-        q_enter<9>();
+        q_enter<4>();  // 1 id + 2 row + 1 weight DMA, issued after the planes
         dslot = slot == 0 ? 2 : slot - 1;
         q_dma_only(f_ahead(p, 2 * c + 1, 2), lds, dslot, w, lo);
         slot = q_next(slot);
       }
 #pragma unroll 1
       for (int u = 2 * KS; u < p.NU; ++u) {
-        q_enter<5>();
+        q_enter<0>();
         const int dslot = slot == 0 ? 2 : slot - 1;
         q_dma_only(f_ahead(p, u, 2), lds, dslot, w, lo);
         slot = q_next(slot);
@@ -425,10 +497,18 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
     asm volatile("" : "+s"(W1), "+s"(W2));  // (loaded once per row block, selected per unit)
     // (forming step s + 1's A at the end of step s's half-1 unit, before the barrier, measured the same:
     // 0.3086-0.3097 vs 0.3094-0.3098 ms, profiles/r05/ab_fused.txt -- not kept)
+    // The fragment ring restarts at every half-0 unit and is carried into the half-1 unit: a 13 + 12-tile K step
+    // shifts the three-register rotation by one, and this loop is rolled (KS is a run-time value).  Unrolling it
+    // by three with a remainder would carry the ring through the whole layer; not built -- the half-0 head
+    // forms the step's A operand (rows, FM, split) after the barrier anyway.
+    f32x4 bq1[3][3];
 #pragma unroll 1
     for (int c = 0; c < KS; ++c, ++s) {
-      q_enter<5>();  // previous unit: (c - 1, half 1) or the previous row block's last layer-3 unit, 5 DMAs
+      F_PROBE_DECL(pr1, blockIdx.x == 0 && it == 1 && c == kFProbeC1, 0);
+      F_PROBE_AT(pr1, 0);
+      q_enter<0>();  // previous unit: (c - 1, half 1) or the previous row block's last layer-3 unit: planes only
       F_USTAMP(it, 2 * c);
+      F_PROBE_AT(pr1, 1);  // (after the unit stamp's own store: the gap to the first MFMA is clean)
       // step s + 1's ids landed two steps ago (its id DMA rode step s - 2; every q_enter since waited for it)
       const FRowIds nid = f_row_ids(wl, s + 1, lane);
       prep(s);
@@ -438,19 +518,21 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
       // ahead of the unit's first MFMA (k_head_s3.hip's order) cost 2 % (0.3142-0.3162 vs 0.3088-0.3111 ms)
       const int sn = s;
       auto extra = [&](int t) {
-        if (t == (kLate ? 0 : 6)) id_dma(sn + 3);
-        if (t == (kLate ? 1 : 8)) f_row_dma_ids(p, wl, sn + 1, lane, nid, 0);
-        if (t == (kLate ? 2 : 10)) f_row_dma_ids(p, wl, sn + 1, lane, nid, 1);
-        if (t == (kLate ? 3 : 11)) f_row_dma_ids(p, wl, sn + 1, lane, nid, 2);
+        if (t == 6) id_dma(sn + 3);
+        if (t == 8) f_row_dma_ids(p, wl, sn + 1, lane, nid, 0);
+        if (t == 10) f_row_dma_ids(p, wl, sn + 1, lane, nid, 1);
+        if (t == 11) f_row_dma_ids(p, wl, sn + 1, lane, nid, 2);
       };
-      q_unit<kQUT, 0, kQNT, 2, kQN, kDoff>(lds + slot * kQUnit, fb, ah, am, al, h1, f_ahead1(W1, W2, c, KS, 0), lds, dslot, w, lo,
-                                          true, extra);
+      const char* ub0 = lds + slot * kQUnit;
       slot = q_next(slot);
-      q_enter<9>();  // previous unit: 1 id + 2 row + 1 weight + 5 plane DMAs
+      const char* ub1 = lds + slot * kQUnit;
+      q_unit_ring<kQUT, 0, kQNT, 2, 0, true, true>(ub0, ub1, fb, ah, am, al, h1, bq1, f_ahead1(W1, W2, c, KS, 0), lds, dslot,
+                                                   w, lo, F_PROBED(extra, pr1));
+      q_enter<4>();  // previous unit: 1 id + 2 row + 1 weight DMA after its planes
       F_USTAMP(it, 2 * c + 1);
       dslot = slot == 0 ? 2 : slot - 1;
-      q_unit<kQNT - kQUT, kQUT, kQNT, 2, kQN, kDoff>(lds + slot * kQUnit, fb, ah, am, al, h1, f_ahead1(W1, W2, c, KS, 1), lds,
-                                                    dslot, w, lo);
+      q_unit_ring<kQNT - kQUT, kQUT, kQNT, 2, q_ring_phase<2>(0, kQUT), false, false>(
+          ub1, ub1, fb, ah, am, al, h1, bq1, f_ahead1(W1, W2, c, KS, 1), lds, dslot, w, lo);
       slot = q_next(slot);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -483,29 +565,35 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
 #pragma unroll
     for (int t = 0; t < kQNT; ++t) h2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int sb2 = s;  // (b2 goes to A slot (sb2 - 1) & 1: f_b2_dma)
-#pragma unroll
-    for (int c = 0; c < kFKS2; ++c) {
-      q_enter<5>();
+    // the fragment ring is carried through all 26 units (the phase of unit (c, half) is a constant)
+    f32x4 bq2[RMX_FUSED_PF2 + 1][3];
+    f_static_for<kFKS2>([&](auto C) {
+      constexpr int c = decltype(C)::value;
+      constexpr int kPh0 = (c * kQNT) % (RMX_FUSED_PF2 + 1), kPh1 = q_ring_phase<RMX_FUSED_PF2>(kPh0, kQUT);
+      F_PROBE_DECL(pr2, blockIdx.x == 0 && it == 1 && c == kFProbeC2, 1);
+      F_PROBE_AT(pr2, 0);
+      q_enter<0>();
+      F_PROBE_AT(pr2, 1);
       bf16x8 ah, am, al;
       const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-      split3(h1[2 * c], 2 * c + 1 < kQNT ? h1[2 * c + 1] : z, ah, am, al);
+      constexpr int c1 = 2 * c + 1 < kQNT ? 2 * c + 1 : 0;
+      split3(h1[2 * c], 2 * c + 1 < kQNT ? h1[c1] : z, ah, am, al);
       int dslot = slot == 0 ? 2 : slot - 1;
       // unit (0, half 0) also DMAs b2 into this wave's free A slot, at its last tile (after the 5 plane DMAs)
       auto b2x = [&](int t) {
         if (c == 0 && t == kQUT - 1) f_b2_dma(p, wl, sb2, lane);
       };
-      q_unit<kQUT, 0, kQNT, RMX_FUSED_PF2, kQN, kDoff>(lds + slot * kQUnit, fb, ah, am, al, h2, f_src23(p, 2 * c + 2),
-                                                       lds, dslot, w, lo, true, b2x);
+      const char* ub0 = lds + slot * kQUnit;
       slot = q_next(slot);
-      if (c == 0)
-        q_enter<7>();  // 5 plane DMAs + the 2 of b2
-      else
-        q_enter<5>();
+      const char* ub1 = lds + slot * kQUnit;
+      q_unit_ring<kQUT, 0, kQNT, RMX_FUSED_PF2, kPh0, c == 0, true>(ub0, ub1, fb, ah, am, al, h2, bq2, f_src23(p, 2 * c + 2),
+                                                                    lds, dslot, w, lo, F_PROBED(b2x, pr2));
+      q_enter<c == 0 ? 2 : 0>();  // (the 2 DMAs of b2 came after unit (0, half 0)'s planes)
       dslot = slot == 0 ? 2 : slot - 1;
-      q_unit<kQNT - kQUT, kQUT, kQNT, RMX_FUSED_PF2, kQN, kDoff>(lds + slot * kQUnit, fb, ah, am, al, h2, f_src23(p, 2 * c + 3),
-                                                     lds, dslot, w, lo);
       slot = q_next(slot);
-    }
+      q_unit_ring<kQNT - kQUT, kQUT, kQNT, RMX_FUSED_PF2, kPh1, false, c + 1 < kFKS2>(
+          ub1, lds + slot * kQUnit, fb, ah, am, al, h2, bq2, f_src23(p, 2 * c + 3), lds, dslot, w, lo);
+    });
     __builtin_amdgcn_sched_barrier(0);
     {
       // b2 from this wave's A slot (its DMA landed units ago: every later q_enter waited for it)
@@ -519,9 +607,9 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
     // ---- layer 3 + the output dot ----
     F_STAMP(it, 3);
     float part = 0.f;
-    f_layer3<0, kDoff>(p, lds, prm, h2, slot, w, lane, lo, fb, part);
+    f_layer3<0>(p, lds, prm, h2, slot, w, lane, lo, fb, part);
     F_STAMP(it, 4);
-    f_layer3<1, kDoff>(p, lds, prm, h2, slot, w, lane, lo, fb, part);
+    f_layer3<1>(p, lds, prm, h2, slot, w, lane, lo, fb, part);
     F_STAMP(it, 5);
     // ---- head: the four lane groups' columns, then bias, CAddTable, sigmoid (out_finish_kernel's order) ----
     part += __shfl_xor(part, 16);
@@ -538,11 +626,6 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
       oa.out[m] = 1.0f / (1.0f + expf(-tt));
     }
   }
-  };
-  if (late)
-    body(std::integral_constant<int, 1>{});
-  else
-    body(std::integral_constant<int, 0>{});
   // the ring's trailing DMAs (units 0 / 1 of a row block that does not exist, the next block's ids / rows)
   // land before the block's LDS is released
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -558,13 +641,15 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
 
 #if RMX_FUSED_DIAG & 1
 // out: [8 waves][4 row blocks][6 stamps], [8 waves][4] (memtime, memrealtime at start and end), then
-// [8 waves][80] row block 1's layer-1 unit entries
+// [8 waves][80] row block 1's layer-1 unit entries, then [8 waves][2 units][4 points] inside two units
 extern "C" int rmx_diag_fused(unsigned long long* out) {
   RMX_HIP(hipDeviceSynchronize());
   RMX_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fused_t), sizeof(g_fused_t)));
   RMX_HIP(hipMemcpyFromSymbol(out + sizeof(g_fused_t) / 8, HIP_SYMBOL(g_fused_clk), sizeof(g_fused_clk)));
   RMX_HIP(hipMemcpyFromSymbol(out + (sizeof(g_fused_t) + sizeof(g_fused_clk)) / 8, HIP_SYMBOL(g_fused_u),
                               sizeof(g_fused_u)));
+  RMX_HIP(hipMemcpyFromSymbol(out + (sizeof(g_fused_t) + sizeof(g_fused_clk) + sizeof(g_fused_u)) / 8,
+                              HIP_SYMBOL(g_fused_r), sizeof(g_fused_r)));
   return RMX_OK;
 }
 #endif
@@ -627,7 +712,6 @@ int launch_tower_fused_s3(hipStream_t s, const DenseLayer& L1, const DenseLayer&
   p.b3 = L3.b;
   p.oa = oa;
   p.prio = tuning_get("fused_prio", 0);
-  p.dma_split = tuning_get("fused_dma_split", 2);
   hipLaunchKernelGGL(tower_fused_s3_kernel, dim3(grid), dim3(kQThreads), kFLds, s, p);
   RMX_HIP(hipGetLastError());
   return RMX_OK;

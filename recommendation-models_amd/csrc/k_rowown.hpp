@@ -72,6 +72,14 @@ struct QNoExtra {
   __device__ __forceinline__ void operator()(int) const {}
 };
 
+// Diagnostic builds only: an extra functor that declares `probe_tag` is called at the issue of the unit's first
+// MFMA (first<PEND>(): PEND fragment reads of later tiles may stay in flight) and after its last (last())
+// (k_fused_s3.hip's stamps); no functor of librmx.so has one.
+template <class X, class = void>
+struct q_has_probe : std::false_type {};
+template <class X>
+struct q_has_probe<X, std::void_t<typename X::probe_tag>> : std::true_type {};
+
 // One unit: NT column tiles (local tiles 0 .. NT - 1 of the unit's half) of one K step.  acc[T0 + t] +=
 // W_t h^T on the split planes (ah, am, al) of this wave's 16 rows; dma(q) issues the wave's q-th DMA of
 // unit U + 2, one per tile.  The fragments of tile t + 2 are read while tile t's MFMAs run.  extra(t) may
@@ -102,6 +110,9 @@ __device__ __forceinline__ void q_unit(const char* ub, int fb, const bf16x8& ah,
       q_dma<PS>(dsrc, lds, dslot, w, (t - kD0) / kDS, lo);
     extra(t);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (q_has_probe<X>::value) {
+      if (t == 0) extra.template first<3 * PF>();
+    }
     const f32x4* b = bq[t % (PF + 1)];
     const bf16x8 bh = __builtin_bit_cast(bf16x8, b[0]);
     const bf16x8 bm = __builtin_bit_cast(bf16x8, b[1]);
@@ -119,6 +130,67 @@ __device__ __forceinline__ void q_unit(const char* ub, int fb, const bf16x8& ah,
     d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, am, d, 0, 0, 0);
     d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, ah, d, 0, 0, 0);
     acc[T0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, d, 0, 0, 0);
+    if constexpr (q_has_probe<X>::value) {
+      if (t == NT - 1) extra.last();
+    }
+  }
+}
+
+// q_unit for a ring that is validated one unit ahead (k_fused_s3.hip): the barrier at the head of a unit has
+// proven the NEXT unit too, so the fragment prefetch does not stop at the unit's last tiles -- it runs on
+// into tiles 0 .. PF - 1 of the next unit (at `ubn`), and the wave reaches the next barrier with its first
+// fragments in registers or in flight.  bq is the caller's fragment ring, carried from unit to unit: tile t's
+// fragments sit in bq[(PH + t) % (PF + 1)], so the next unit's phase is q_ring_phase (every index stays a
+// compile-time constant).  HEAD: the chain starts here (nothing was prefetched: read tiles 0 .. PF - 1 first,
+// as q_unit does); CARRY: prefetch into the next unit (false in the chain's last unit).  The wave's five plane
+// DMAs ride tiles 0 .. 4, ahead of everything extra(t) issues (callers use tiles >= 5): the wait at the next
+// unit's head counts only those extras.  MFMA order per accumulator as in q_unit.
+template <int PF>
+constexpr int q_ring_phase(int ph, int nt) {
+  return (ph + nt) % (PF + 1);
+}
+template <int NT, int T0, int NA, int PF, int PH, bool HEAD, bool CARRY, int PS = kQN, class X = QNoExtra>
+__device__ __forceinline__ void q_unit_ring(const char* ub, const char* ubn, int fb, const bf16x8& ah, const bf16x8& am,
+                                            const bf16x8& al, f32x4 (&acc)[NA], f32x4 (&bq)[PF + 1][3],
+                                            const bf16_t* dsrc, char* lds, int dslot, int w, int lo,
+                                            const X& extra = X()) {
+  static_assert(PF >= 1 && PF < NT && PH >= 0 && PH <= PF, "fragment ring");
+  int fbu = fb;
+  asm volatile("" : "+v"(fbu));
+  auto ldb = [&](const char* u, int t, f32x4* b) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const f32x4*>(u + fbu + pl * (kQUT * 1024) + t * 1024);
+  };
+  if constexpr (HEAD) {
+#pragma unroll
+    for (int t = 0; t < PF; ++t) ldb(ub, t, bq[(PH + t) % (PF + 1)]);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t + PF < NT)
+      ldb(ub, t + PF, bq[(PH + t + PF) % (PF + 1)]);
+    else if constexpr (CARRY)
+      ldb(ubn, t + PF - NT, bq[(PH + t + PF) % (PF + 1)]);
+    if (t < kQQ) q_dma<PS>(dsrc, lds, dslot, w, t, lo);
+    extra(t);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (q_has_probe<X>::value) {
+      if (t == 0) extra.template first<3 * PF>();
+    }
+    const f32x4* b = bq[(PH + t) % (PF + 1)];
+    const bf16x8 bh = __builtin_bit_cast(bf16x8, b[0]);
+    const bf16x8 bm = __builtin_bit_cast(bf16x8, b[1]);
+    const bf16x8 bl = __builtin_bit_cast(bf16x8, b[2]);
+    f32x4 d = acc[T0 + t];
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, am, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, am, d, 0, 0, 0);
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, ah, d, 0, 0, 0);
+    acc[T0 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, d, 0, 0, 0);
+    if constexpr (q_has_probe<X>::value) {
+      if (t == NT - 1) extra.last();
+    }
   }
 }
 

@@ -5,7 +5,9 @@ RMX_LIB=vbuild/fdiag/librmx.so python tools/diag_fused.py).  Runs ~2.5 s of back
 (DVFS settles), then one forward, and prints per row block and wave: layer 1 (+ first order + FM), the FM
 epilogue + h1 bias / ReLU, layer 2, layer 3 half 0, layer 3 half 1, the head, with the MFMA floor of
 each layer (16 cycles per v_mfma_f32_16x16x32_bf16, two waves per SIMD) and the clock measured in the
-kernel (s_memtime / s_memrealtime at 100 MHz)."""
+kernel (s_memtime / s_memrealtime at 100 MHz); then, inside one layer-1 half-0 unit and one layer-2 unit of
+row block 1, the wait + barrier at the unit's head, the gap from the barrier to the first MFMA and the MFMA
+stream (the stamped build spills registers the shipped kernel does not: read shares, not cycles)."""
 import argparse
 import ctypes
 import os
@@ -47,7 +49,8 @@ m.forward_ids(t, B, ids, out)
 ctx.sync()
 NW, NIT, NPH = 8, 4, 6
 NU1 = 80
-buf = (ctypes.c_ulonglong * (NW * NIT * NPH + NW * 4 + NW * NU1))()
+NPR = 2 * 4  # two probed units x four points (g_fused_r)
+buf = (ctypes.c_ulonglong * (NW * NIT * NPH + NW * 4 + NW * NU1 + NW * NPR))()
 fn = rmx._lib.lib.rmx_diag_fused
 fn.argtypes = [ctypes.c_void_p]
 assert fn(buf) == 0
@@ -84,7 +87,7 @@ if tot:
     fl = sum(floor.values())
     print("row block 0 -> 1, whole: mean %.0f cycles, MFMA floor %d (eff %.3f)" % (np.mean(tot), fl, fl / np.mean(tot)))
 
-u = np.array(buf[NW * NIT * NPH + NW * 4:], dtype=np.int64).reshape(NW, NU1)
+u = np.array(buf[NW * NIT * NPH + NW * 4:NW * NIT * NPH + NW * 4 + NW * NU1], dtype=np.int64).reshape(NW, NU1)
 nu = 2 * KS
 ends = np.concatenate([u[:, 1:nu], st[:, 1, 1:2]], axis=1)  # unit k ends at unit k + 1's entry (last: layer 1 end)
 d = ends - u[:, :nu]
@@ -94,3 +97,18 @@ h0, h1 = d[:, 0::2].mean(axis=0), d[:, 1::2].mean(axis=0)
 print("  half 0: " + " ".join("%d" % x for x in h0))
 print("  half 1: " + " ".join("%d" % x for x in h1))
 print("  mean half 0 %.0f, half 1 %.0f" % (h0.mean(), h1.mean()))
+
+# inside two units of row block 1 (g_fused_r): before q_enter, after its barrier, at the first MFMA's issue,
+# after the last MFMA.  Each stamp costs its own s_memtime round trip (about 40 cycles, inside the interval
+# that follows it); layer 1's barrier interval also holds the unit-entry stamp above.
+pr = np.array(buf[NW * NIT * NPH + NW * 4 + NW * NU1:], dtype=np.int64).reshape(NW, 2, 4)
+for k, nm in enumerate(["layer 1 (c = 10, half 0)", "layer 2 (c = 6, half 0)"]):
+    v = pr[:, k]
+    if not v[:, 0].all():
+        continue
+    wait, gap, mf = v[:, 1] - v[:, 0], v[:, 2] - v[:, 1], v[:, 3] - v[:, 2]
+    print("unit probe, %s, cycles per wave 0..7:" % nm)
+    print("  vmcnt wait + barrier      : " + " ".join("%5d" % x for x in wait) + "   mean %.0f" % wait.mean())
+    print("  barrier exit -> first MFMA: " + " ".join("%5d" % x for x in gap) + "   mean %.0f" % gap.mean())
+    print("  first MFMA -> last MFMA   : " + " ".join("%5d" % x for x in mf) + "   mean %.0f" % mf.mean())
+    print("  barrier exit, spread over the waves: %d cycles" % (v[:, 1].max() - v[:, 1].min()))
