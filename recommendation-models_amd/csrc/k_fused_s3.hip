@@ -52,22 +52,17 @@
 //
 // Parity: each layer's products and K order are the head's / tail's, so h1, h2 and the logit's summands
 // are the same fp32 values; the FM + first order are encoder_k16_kernel<1>'s arithmetic (bit-identical y1 +
-// y2), and the head applies out_finish_kernel's order.  The predictions are therefore bitwise those of
-// head + tail (tests/test_fused_s3.py), and held to 1e-5 against the fp64 oracle.
+// y2), and the head is the one function of every kernel (k_gemm.hpp out_head).  The predictions are therefore
+// bitwise those of head + tail (tests/test_fused_s3.py), and held to 1e-5 against the fp64 oracle.
 #include "k_rowown.hpp"
 
 namespace rmx {
 namespace {
 using namespace rowown;
 
-constexpr int kFMaxF = 40;                       // fields (K = 16 F <= 640, 20 K steps)
-constexpr int kFA = 2 * 2 * 16 * 64;             // per wave: 2 slots x [2 fields][16 samples][64 B]
-constexpr int kFId = 4 * 128;                    // per wave: 4 slots x [2 fields][16] ids
-constexpr int kFWr = 2 * 128;                    // per wave: 2 slots x [2 fields][16] first-order weights
-constexpr int kFWave = kFA + kFId + kFWr;
 constexpr int kFKS2 = 13;                        // K steps of layers 2 and 3 (Kpad 416)
 constexpr int kFPrm = 3 * kQN;                   // b3 | wo | b1 in LDS
-constexpr size_t kFLds = (size_t)kQSlots * kQUnit + (size_t)kQW * kFWave + sizeof(float) * kFPrm;
+constexpr size_t kFLds = (size_t)kQSlots * kQUnit + (size_t)kQW * kGWave + sizeof(float) * kFPrm;
 static_assert(kFLds <= 160 * 1024, "LDS budget");
 static_assert(sizeof(float) * kQN <= 2048, "b2 fits a wave's free A slot (f_b2_dma)");
 
@@ -91,7 +86,7 @@ static_assert(sizeof(float) * kQN <= 2048, "b2 fits a wave's free A slot (f_b2_d
 constexpr int kFDiagIt = 4, kFDiagPh = 6;
 __device__ unsigned long long g_fused_t[kQW][kFDiagIt][kFDiagPh];  // [wave][row block][phase]
 __device__ unsigned long long g_fused_clk[kQW][4];                   // memtime / memrealtime at start, end
-__device__ unsigned long long g_fused_u[kQW][2 * kFMaxF];            // row block 1's layer-1 units, at entry
+__device__ unsigned long long g_fused_u[kQW][2 * kGMaxF];            // row block 1's layer-1 units, at entry
 // one lane's vector store (the value and the address depend on the lane: never a scalar-cache store)
 __device__ __forceinline__ void f_stamp(unsigned long long* dst, int lane, unsigned long long v) {
   int l = lane;
@@ -163,11 +158,7 @@ struct FProbed {
 struct FusedS3Args {
   int M, F, KS, NU;       // KS = ceil(F / 2) layer-1 K steps; NU = 2 KS + 52 units per row block
   QRows rows;             // full / half row blocks (k_rowown.hpp)
-  const int32_t* ids;     // [M][F]
-  const float* table;     // row of id at table + (id << gsh) (16 fp32: k = 16)
-  int gsh;
-  const float* wtab;      // first-order weight of id at wtab[id << wsh]
-  int wsh;
+  GatherArgs ga;          // ids [M][F], table, first-order weights (k_rowown.hpp)
   const bf16_t* W1;       // [KS][3][416][32] split planes (DenseLayer::W3)
   const float* b1;        // [416]
   const bf16_t* W2;       // [13][3][416][32]
@@ -198,7 +189,7 @@ __device__ __forceinline__ const bf16_t* f_unit_src(const FusedS3Args& p, int u)
     c = v - half * kFKS2;
     W = p.W3;
   }
-  return W + (int64_t)(c * 3 * kQN + half * kQUT * 16) * 32;
+  return q_plane_src(W, c, half);
 }
 
 // the source of unit u + d (d <= 2), wrapping into the next row block's first units (the same weights)
@@ -214,7 +205,7 @@ __device__ __forceinline__ const bf16_t* f_ahead1(const bf16_t* W1, const bf16_t
   const bool l1 = c + 1 < KS;
   const bf16_t* W = l1 ? W1 : W2;
   const int cc = l1 ? c + 1 : 0;
-  return W + (int64_t)(cc * 3 * kQN + half * kQUT * 16) * 32;
+  return q_plane_src(W, cc, half);
 }
 
 // unit V (a compile-time constant after unrolling) of layers 2 + 3 (V < 52), or V - 52 of the next row block's
@@ -234,77 +225,50 @@ __device__ __forceinline__ const bf16_t* f_src23(const FusedS3Args& p, int V) {
     c = (V - 4 * kFKS2) >> 1;
     half = (V - 4 * kFKS2) & 1;
   }
-  return W + (int64_t)(c * 3 * kQN + half * kQUT * 16) * 32;
+  return q_plane_src(W, c, half);
 }
 
-// ids of K step c of the row block at row0 (nw waves own rows) into id slot `slot` (lanes 0 .. 31: field
-// 2c + (L >> 4) of sample L & 15; past M or F, or for a wave without rows: -1)  (k_head_s3.hip h_id_dma)
-__device__ __forceinline__ void f_id_dma(const FusedS3Args& p, char* wl, int row0, int nw, int c, int slot, int w,
-                                         int lane) {
-  int f = lane >> 4, r = lane & 15;
-  asm volatile("" : "+v"(f), "+v"(r));
-  const int m = row0 + w * 16 + r, fld = 2 * c + f;
-  const bool ok = w < nw && m < p.M && fld < p.F;
-  const int32_t* src = ok ? p.ids + (int64_t)m * p.F + fld : g_rmx_neg1;
-  if (lane < 32)
-    lds_dma<4>(src, wl + kFA + slot * 128);
+// Layer 1's row / weight DMAs from ids already in registers (k_rowown.hpp g_row_dma_ids), with the timing
+// probes of diagnostic builds (results wrong)
+__device__ __forceinline__ void f_row_dma_ids(const GatherArgs& ga, char* wl, int s, int lane, const GRowIds& q,
+                                              int part) {
+#if RMX_FUSED_DIAG & 4  // no row / weight gathers in layer 1
+  return;
+#elif RMX_FUSED_DIAG & 2  // every gather reads the lane's own row of the table's first 16 (cached)
+  if (part < 2) {
+    int g = swz_slot(lane >> 2, lane & 3);
+    asm volatile("" : "+v"(g));
+    lds_dma<16>(ga.table + ((int64_t)(lane >> 2) << ga.gsh) + 4 * g, wl + (s & 1) * 2048 + part * 1024);
+    return;
+  }
+#endif
+  g_row_dma_ids(ga, wl, s, lane, q, part);
 }
-
-// rows (2 DMAs) and first-order weights (lanes 0 .. 31) of the wave's step s, from the ids in id slot s & 3,
-// into A slot s & 1 / weight slot s & 1  (k_head_s3.hip h_row_dma)
-// part 0 / 1: the row of field 2c / 2c + 1; part 2: the weights; -1: all three
-__device__ __forceinline__ void f_row_dma(const FusedS3Args& p, char* wl, int s, int lane, int part = -1) {
-  const int* ids = reinterpret_cast<const int*>(wl + kFA + (s & 3) * 128);
+// All three parts at once, each id read at its DMA (the prologue, the waves without rows).  This kernel's own
+// copy, kept on purpose: k_rowown.hpp's g_row_dma forms every address before the first DMA, as k_head_s3.hip
+// issues them, and built with that one this kernel spilled a second VGPR (scratch 8 -> 12 B per lane); built
+// from g_row_ids + three g_row_dma_ids it kept its registers but not its code (the prologue and the loops of
+// the waves without rows came out in another order).  With this copy the kernel is instruction for
+// instruction what it was.
+__device__ __forceinline__ void f_row_dma(const GatherArgs& ga, char* wl, int s, int lane) {
+  const int* ids = reinterpret_cast<const int*>(wl + kGA + (s & 3) * 128);
   int r = lane >> 2, g = swz_slot(lane >> 2, lane & 3), lw = lane & 31;
   asm volatile("" : "+v"(r), "+v"(g), "+v"(lw));
   const float* zero16 = g_rmx_zero16;
   char* a = wl + (s & 1) * 2048;
-  if (part < 0 || part == 0) {
+  {
     const int id0 = ids[r];
-    lds_dma<16>(id0 >= 0 ? p.table + ((int64_t)id0 << p.gsh) + 4 * g : zero16, a);
+    lds_dma<16>(id0 >= 0 ? ga.table + ((int64_t)id0 << ga.gsh) + 4 * g : zero16, a);
   }
-  if (part < 0 || part == 1) {
+  {
     const int id1 = ids[16 + r];
-    lds_dma<16>(id1 >= 0 ? p.table + ((int64_t)id1 << p.gsh) + 4 * g : zero16, a + 1024);
+    lds_dma<16>(id1 >= 0 ? ga.table + ((int64_t)id1 << ga.gsh) + 4 * g : zero16, a + 1024);
   }
-  if (part < 0 || part == 2) {
+  {
     const int idw = ids[lw];
     if (lane < 32)
-      lds_dma<4>(idw >= 0 ? p.wtab + ((int64_t)idw << p.wsh) : zero16, wl + kFA + kFId + (s & 1) * 128);
+      lds_dma<4>(idw >= 0 ? ga.wtab + ((int64_t)idw << ga.wsh) : zero16, wl + kGA + kGId + (s & 1) * 128);
   }
-}
-
-// The same DMAs from ids already in registers (round 6): step s + 1's three ids (the rows of fields 2c, 2c + 1
-// and the weight) are read from their id slot at the start of step s's half-0 unit, beside prep's reads.
-// Read at the DMA (f_row_dma inside the MFMA stream), each id needed an s_waitcnt lgkmcnt(0) that also drained
-// the B fragments prefetched for the next tiles -- three times per half-0 unit.
-struct FRowIds {
-  int id0, id1, idw;
-};
-__device__ __forceinline__ FRowIds f_row_ids(char* wl, int s, int lane) {
-  const int* ids = reinterpret_cast<const int*>(wl + kFA + (s & 3) * 128);
-  int r = lane >> 2, lw = lane & 31;
-  asm volatile("" : "+v"(r), "+v"(lw));
-  return FRowIds{ids[r], ids[16 + r], ids[lw]};
-}
-__device__ __forceinline__ void f_row_dma_ids(const FusedS3Args& p, char* wl, int s, int lane, const FRowIds& q,
-                                              int part) {
-#if RMX_FUSED_DIAG & 4  // timing probe: no row / weight gathers in layer 1 (results wrong)
-  return;
-#endif
-  int g = swz_slot(lane >> 2, lane & 3);
-  asm volatile("" : "+v"(g));
-  const float* zero16 = g_rmx_zero16;
-  char* a = wl + (s & 1) * 2048;
-#if RMX_FUSED_DIAG & 2  // timing probe: every gather reads the lane's own row of the table's first 16 (cached)
-  if (part == 0) lds_dma<16>(p.table + ((int64_t)(lane >> 2) << p.gsh) + 4 * g, a);
-  if (part == 1) lds_dma<16>(p.table + ((int64_t)(lane >> 2) << p.gsh) + 4 * g, a + 1024);
-#else
-  if (part == 0) lds_dma<16>(q.id0 >= 0 ? p.table + ((int64_t)q.id0 << p.gsh) + 4 * g : zero16, a);
-  if (part == 1) lds_dma<16>(q.id1 >= 0 ? p.table + ((int64_t)q.id1 << p.gsh) + 4 * g : zero16, a + 1024);
-#endif
-  if (part == 2 && lane < 32)
-    lds_dma<4>(q.idw >= 0 ? p.wtab + ((int64_t)q.idw << p.wsh) : zero16, wl + kFA + kFId + (s & 1) * 128);
 }
 
 // The biases of layers 1 and 2 come from LDS (round 6).  Read with scalar loads (round 5), the compiler
@@ -338,7 +302,6 @@ __device__ __forceinline__ void f_static_for(F&& f) {
 template <int HF>
 __device__ __forceinline__ void f_layer3(const FusedS3Args& p, char* lds, const float* prm, f32x4 (&h2)[kQNT],
                                          int& slot, int w, int lane, int lo, int fb, float& part) {
-  const int g = lane >> 4;
   f32x4 acc[kQUT];
 #pragma unroll
   for (int t = 0; t < kQUT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -353,31 +316,14 @@ __device__ __forceinline__ void f_layer3(const FusedS3Args& p, char* lds, const 
     bf16x8 ah, am, al;
     constexpr int c1 = 2 * c + 1 < kQNT ? 2 * c + 1 : 0;
     split3(h2[2 * c], 2 * c + 1 < kQNT ? h2[c1] : z, ah, am, al);
-    const int dslot = slot == 0 ? 2 : slot - 1;  // (slot + 2) mod 3
+    const int dslot = q_dslot(slot);
     const char* ub = lds + slot * kQUnit;
     slot = q_next(slot);
     const bf16_t* src = f_src23(p, 2 * kFKS2 + HF * kFKS2 + c + 2);
     q_unit_ring<NTU, 0, kQUT, RMX_FUSED_PF3, (c * NTU) % (RMX_FUSED_PF3 + 1), c == 0, c + 1 < kFKS2>(
         ub, lds + slot * kQUnit, fb, ah, am, al, acc, bq, src, lds, dslot, w, lo);
   });
-  // the output dot over this half's columns: ReLU(acc + b3)[n] * wo[n], n = 16 (13 HF + t) + 4 g + q
-  constexpr int NT = HF == 0 ? kQUT : kQNT - kQUT;
-  __builtin_amdgcn_sched_barrier(0);
-  int g4 = 4 * g;
-  asm volatile("" : "+v"(g4));
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int n0 = 16 * (kQUT * HF + t) + g4;
-    const f32x4 bb = *reinterpret_cast<const f32x4*>(prm + n0);
-    const f32x4 wv = *reinterpret_cast<const f32x4*>(prm + kQN + n0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float v = acc[t][r] + bb[r];
-      v = v > 0.f ? v : 0.f;
-      part += v * wv[r];
-    }
-  }
-  asm volatile("" : "+v"(part));  // (the dot is done here: sunk past half 1 it kept 13 accumulators alive)
+  q_dot_half<HF>(acc, prm, prm + kQN, lane >> 4, part);
 }
 
 __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Args p) {
@@ -385,8 +331,8 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
   char* lds = fsmem;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r16 = lane & 15;
-  char* wl = fsmem + kQSlots * kQUnit + w * kFWave;  // this wave's rows / ids / weights
-  float* prm = reinterpret_cast<float*>(fsmem + kQSlots * kQUnit + kQW * kFWave);  // b3 | wo | b1
+  char* wl = fsmem + kQSlots * kQUnit + w * kGWave;  // this wave's rows / ids / weights
+  float* prm = reinterpret_cast<float*>(fsmem + kQSlots * kQUnit + kQW * kGWave);  // b3 | wo | b1
   const int nit = p.rows.nit(blockIdx.x);
   const int KS = p.KS;
   const OutArgs& oa = p.oa;
@@ -407,29 +353,18 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
   }
   // (a separate loop: a third source in the select above hit "illegal VGPR to SGPR copy" in the compiler)
   for (int i = tid; i < kQN; i += kQThreads) prm[2 * kQN + i] = p.b1[i];
-  int lo = (lane >> 2) * 32 + swz_slot(lane >> 2, lane & 3) * 8;
-  asm volatile("" : "+v"(lo));
+  Q_LANE_LO(lo, lane);
   const int fb = q_fbase(lane);
 
-  // the wave's layer-1 steps s = 0, 1, ... run over its row blocks: step s is K step s % KS of row block
-  // blockIdx.x + (s / KS) gridDim.x; its ring slots are s & 3 (ids) and s & 1 (rows, weights)
-  auto id_dma = [&](int s) {
-    const int it = s / KS, c = s - it * KS;
-    int row0, nw;
-    p.rows.desc(blockIdx.x, it, row0, nw);
-    f_id_dma(p, wl, row0, nw, c, s & 3, w, lane);
-  };
+  // the wave's layer-1 steps s = 0, 1, ... of the gathered-A stream run on over its row blocks (k_rowown.hpp)
+  auto id_dma = [&](int s) { g_id_dma_step(p.ga.ids, p.M, p.F, p.rows, KS, wl, s, w, lane); };
   if (nit > 0) {
-    for (int s = 0; s < 3; ++s) id_dma(s);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    f_row_dma(p, wl, 0, lane);
-#pragma unroll
-    for (int qq = 0; qq < kQQ; ++qq) q_dma(f_unit_src(p, 0), lds, 0, w, qq, lo);
-#pragma unroll
-    for (int qq = 0; qq < kQQ; ++qq) q_dma(f_unit_src(p, 1), lds, 1, w, qq, lo);
+    for (int i = 0; i < 3; ++i) id_dma(i);
+    q_drain();
+    f_row_dma(p.ga, wl, 0, lane);
+    Q_PROLOGUE(f_unit_src(p, 0), f_unit_src(p, 1), lds, w, lo);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();  // prm staged; this wave's units 0 and 1 landed (q_enter's barrier covers the rest)
+  q_meet();
 
   int slot = 0, s = 0;
   // Every wave runs one schedule: the unit's five plane DMAs at tiles 0 .. 4, layer 1's id / row / weight DMAs at
@@ -447,22 +382,22 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
 #pragma unroll 1
       for (int c = 0; c < KS; ++c, ++s) {
         q_enter<0>();
-        int dslot = slot == 0 ? 2 : slot - 1;
+        int dslot = q_dslot(slot);
         q_dma_only(f_ahead(p, 2 * c, 2), lds, dslot, w, lo);
         __builtin_amdgcn_sched_barrier(0);
         id_dma(s + 3);
-        f_row_dma(p, wl, s + 1, lane);
+        f_row_dma(p.ga, wl, s + 1, lane);
         __builtin_amdgcn_sched_barrier(0);
         slot = q_next(slot);
         q_enter<4>();  // 1 id + 2 row + 1 weight DMA, issued after the planes
-        dslot = slot == 0 ? 2 : slot - 1;
+        dslot = q_dslot(slot);
         q_dma_only(f_ahead(p, 2 * c + 1, 2), lds, dslot, w, lo);
         slot = q_next(slot);
       }
 #pragma unroll 1
       for (int u = 2 * KS; u < p.NU; ++u) {
         q_enter<0>();
-        const int dslot = slot == 0 ? 2 : slot - 1;
+        const int dslot = q_dslot(slot);
         q_dma_only(f_ahead(p, u, 2), lds, dslot, w, lo);
         slot = q_next(slot);
       }
@@ -483,7 +418,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
       const char* a = wl + (ss & 1) * 2048;
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(a + o);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(a + 1024 + o);
-      const float* wr = reinterpret_cast<const float*>(wl + kFA + kFId + (ss & 1) * 128);
+      const float* wr = reinterpret_cast<const float*>(wl + kGA + kGId + (ss & 1) * 128);
       {
 #pragma clang fp contract(off)
         fm_accum(a0, a1, fs, fq);  // (SecondOrderEncoder sums, field order, k_gemm.hpp)
@@ -510,18 +445,18 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
       F_USTAMP(it, 2 * c);
       F_PROBE_AT(pr1, 1);  // (after the unit stamp's own store: the gap to the first MFMA is clean)
       // step s + 1's ids landed two steps ago (its id DMA rode step s - 2; every q_enter since waited for it)
-      const FRowIds nid = f_row_ids(wl, s + 1, lane);
+      const GRowIds nid = g_row_ids(wl, s + 1, lane);
       prep(s);
-      int dslot = slot == 0 ? 2 : slot - 1;
+      int dslot = q_dslot(slot);
       // the ids (3 steps ahead), rows and weights (1 step ahead) ride tiles 6, 8, 10, 11 of the unit's MFMA
       // stream, after its 5 plane DMAs: an LDS-DMA issue can hold its wave ~100-200 cycles, and four of them
       // ahead of the unit's first MFMA (k_head_s3.hip's order) cost 2 % (0.3142-0.3162 vs 0.3088-0.3111 ms)
       const int sn = s;
       auto extra = [&](int t) {
         if (t == 6) id_dma(sn + 3);
-        if (t == 8) f_row_dma_ids(p, wl, sn + 1, lane, nid, 0);
-        if (t == 10) f_row_dma_ids(p, wl, sn + 1, lane, nid, 1);
-        if (t == 11) f_row_dma_ids(p, wl, sn + 1, lane, nid, 2);
+        if (t == 8) f_row_dma_ids(p.ga, wl, sn + 1, lane, nid, 0);
+        if (t == 10) f_row_dma_ids(p.ga, wl, sn + 1, lane, nid, 1);
+        if (t == 11) f_row_dma_ids(p.ga, wl, sn + 1, lane, nid, 2);
       };
       const char* ub0 = lds + slot * kQUnit;
       slot = q_next(slot);
@@ -530,7 +465,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
                                                    w, lo, F_PROBED(extra, pr1));
       q_enter<4>();  // previous unit: 1 id + 2 row + 1 weight DMA after its planes
       F_USTAMP(it, 2 * c + 1);
-      dslot = slot == 0 ? 2 : slot - 1;
+      dslot = q_dslot(slot);
       q_unit_ring<kQNT - kQUT, kQUT, kQNT, 2, q_ring_phase<2>(0, kQUT), false, false>(
           ub1, ub1, fb, ah, am, al, h1, bq1, f_ahead1(W1, W2, c, KS, 1), lds, dslot, w, lo);
       slot = q_next(slot);
@@ -578,7 +513,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
       const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
       constexpr int c1 = 2 * c + 1 < kQNT ? 2 * c + 1 : 0;
       split3(h1[2 * c], 2 * c + 1 < kQNT ? h1[c1] : z, ah, am, al);
-      int dslot = slot == 0 ? 2 : slot - 1;
+      int dslot = q_dslot(slot);
       // unit (0, half 0) also DMAs b2 into this wave's free A slot, at its last tile (after the 5 plane DMAs)
       auto b2x = [&](int t) {
         if (c == 0 && t == kQUT - 1) f_b2_dma(p, wl, sb2, lane);
@@ -589,7 +524,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
       q_unit_ring<kQUT, 0, kQNT, RMX_FUSED_PF2, kPh0, c == 0, true>(ub0, ub1, fb, ah, am, al, h2, bq2, f_src23(p, 2 * c + 2),
                                                                     lds, dslot, w, lo, F_PROBED(b2x, pr2));
       q_enter<c == 0 ? 2 : 0>();  // (the 2 DMAs of b2 came after unit (0, half 0)'s planes)
-      dslot = slot == 0 ? 2 : slot - 1;
+      dslot = q_dslot(slot);
       slot = q_next(slot);
       q_unit_ring<kQNT - kQUT, kQUT, kQNT, RMX_FUSED_PF2, kPh1, false, c + 1 < kFKS2>(
           ub1, lds + slot * kQUnit, fb, ah, am, al, h2, bq2, f_src23(p, 2 * c + 3), lds, dslot, w, lo);
@@ -611,7 +546,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
     F_STAMP(it, 4);
     f_layer3<1>(p, lds, prm, h2, slot, w, lane, lo, fb, part);
     F_STAMP(it, 5);
-    // ---- head: the four lane groups' columns, then bias, CAddTable, sigmoid (out_finish_kernel's order) ----
+    // ---- head: the four lane groups' columns, then bias, CAddTable, sigmoid (k_gemm.hpp out_head) ----
     part += __shfl_xor(part, 16);
     part += __shfl_xor(part, 32);
     // (lane made afresh, as for b2: the kernel-start r16 was spilled here, and its reload waited vmcnt(0) --
@@ -619,16 +554,10 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_fused_s3_kernel(FusedS3Arg
     const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int m = row0 + w * 16 + (ln & 15);
     if (ln < 16 && m < p.M) {
-      float y = part;
-      if (oa.has_bo) y = y + oa.bo;
-      float tt = pre + y;
-      tt = tt + oa.beta;
-      oa.out[m] = 1.0f / (1.0f + expf(-tt));
+      oa.out[m] = out_head(oa, part, false, 0.f, false, 0.f, true, pre);
     }
   }
-  // the ring's trailing DMAs (units 0 / 1 of a row block that does not exist, the next block's ids / rows)
-  // land before the block's LDS is released
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  q_drain();  // (the next block's ids / rows, too)
 #if RMX_FUSED_DIAG & 1
   if (blockIdx.x == 0) {
     f_stamp(&g_fused_clk[w][2], lane, __builtin_amdgcn_s_memtime());
@@ -654,16 +583,22 @@ extern "C" int rmx_diag_fused(unsigned long long* out) {
 }
 #endif
 
+// what the kernel itself relies on: F <= 40 fields of k = 16 into three 400-wide split-GEMM layers, b1 and b2
+// present (they are read without a null check).  The launch checks this much; the path choice below asks for
+// more -- a plain per-output bias, no bf16 planes, no extra columns -- as it always did.
+static bool fused_s3_shape(const DenseLayer& L1, const DenseLayer& L2, const DenseLayer& L3, int F) {
+  return F >= 1 && F <= kGMaxF && L1.W3 && L2.W3 && L3.W3 && L1.b && L2.b && L1.K == 16 * F && L1.Npad == kQN &&
+         L2.Npad == kQN && L3.Npad == kQN && L2.K == 400 && L3.K == 400 && L1.N == 400 && L2.N == 400 && L3.N == 400;
+}
+
 bool tower_fused_s3_usable(const DenseLayer& L1, const DenseLayer& L2, const DenseLayer& L3, int M, int F, int k,
                            bool ids) {
-  if (M <= 0 || !ids || k != 16 || F < 1 || F > kFMaxF || !f32_split_enabled()) return false;
-  if (!L1.W3 || !L2.W3 || !L3.W3 || L1.W16 || L2.W16 || L3.W16) return false;
-  if (!(L1.K == 16 * F && L1.N == 400 && L1.Npad == kQN && L1.N1 < 0 && L1.bias_mode == 1 && L1.K1 < 0)) return false;
-  if (!(L2.K == 400 && L2.N == 400 && L3.K == 400 && L3.N == 400 && L2.Npad == kQN && L3.Npad == kQN &&
-        (L2.Kpad + 31) / 32 == kFKS2 && (L3.Kpad + 31) / 32 == kFKS2 && L2.N1 < 0 && L3.N1 < 0 && L2.bias_mode == 1 &&
+  if (M <= 0 || !ids || k != 16 || !f32_split_enabled() || !fused_s3_shape(L1, L2, L3, F)) return false;
+  if (L1.W16 || L2.W16 || L3.W16) return false;
+  if (!(L1.N1 < 0 && L1.bias_mode == 1 && L1.K1 < 0)) return false;
+  if (!((L2.Kpad + 31) / 32 == kFKS2 && (L3.Kpad + 31) / 32 == kFKS2 && L2.N1 < 0 && L3.N1 < 0 && L2.bias_mode == 1 &&
         L3.bias_mode == 1))
     return false;
-  if (!L1.b || !L2.b) return false;
   // knob "s3_fused": 0 off (head + tail), 1 (default) / 2 on.  Round 5 kept it to batches whose full 128-row
   // blocks fill every CU (B = 16,384: head + tail 154.4 M against the fused tower's 147.7 M then,
   // profiles/r05/ab_fused_batch.txt); after round 6's fused-tower work it wins at every batch the small-batch
@@ -675,35 +610,29 @@ bool tower_fused_s3_usable(const DenseLayer& L1, const DenseLayer& L2, const Den
 int launch_tower_fused_s3(hipStream_t s, const DenseLayer& L1, const DenseLayer& L2, const DenseLayer& L3, int M, int F,
                           const int32_t* ids, const float* table, int ld, const float* wtab, int wld,
                           const OutArgs& oa) {
-  if (!ids || !oa.wo || !oa.out || F < 1 || F > kFMaxF || !L1.W3 || !L2.W3 || !L3.W3 || !L1.b || !L2.b ||
-      L1.K != 16 * F || L1.Npad != kQN || L2.Npad != kQN || L3.Npad != kQN || L2.K != 400 || L3.K != 400 ||
-      L1.N != 400 || L2.N != 400 || L3.N != 400) {
+  if (!ids || !oa.wo || !oa.out || !fused_s3_shape(L1, L2, L3, F)) {
     set_error("fp32 fused tower: needs a k = 16 gather (F <= 40, ids) into three 400-wide split-GEMM layers + head");
     return RMX_E_INVALID;
   }
   if (M <= 0) return RMX_OK;
-  const int l = ld > 0 ? ld : 16, wl = wld > 0 ? wld : 1;
-  if ((l & (l - 1)) || l < 16 || (wl & (wl - 1))) {
+  FusedS3Args p{};
+  if (!gather_shifts(ld, wld, p.ga.gsh, p.ga.wsh)) {
     set_error("fp32 fused tower: table / weight strides must be powers of two");
     return RMX_E_INVALID;
   }
-  int dev = 0, ncu = 0;
-  RMX_HIP(hipGetDevice(&dev));
-  RMX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  int ncu = 0;
+  RMX_HIP(cu_count(&ncu));
   RMX_HIP(hipFuncSetAttribute((const void*)tower_fused_s3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)kFLds));
-  FusedS3Args p{};
   p.M = M;
   int grid = 0;
   p.rows = q_rows(M, ncu, grid);
   p.F = F;
   p.KS = (F + 1) / 2;
   p.NU = 2 * p.KS + 4 * kFKS2;
-  p.ids = ids;
-  p.table = table;
-  p.gsh = __builtin_ctz((unsigned)l);
-  p.wtab = wtab;
-  p.wsh = __builtin_ctz((unsigned)wl);
+  p.ga.ids = ids;
+  p.ga.table = table;
+  p.ga.wtab = wtab;
   p.W1 = L1.W3;
   p.b1 = L1.b;
   p.W2 = L2.W3;

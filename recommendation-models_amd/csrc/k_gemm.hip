@@ -42,17 +42,7 @@ __global__ __launch_bounds__(256) void tower_head_kernel(int M, int N, const flo
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o);
   if (lane != 0) return;
-  float y = p;
-  if (oa.has_bo) y = y + oa.bo;
-  if (oa.rowsum) {
-    float rs = 0.f;
-    for (int j = 0; j < oa.rowsum_k; ++j) rs += oa.rowsum[(int64_t)m * oa.rowsum_k + j];
-    y = rs + y;
-  }
-  if (oa.pre2) y = oa.pre2[m] + y;
-  float t = oa.pre ? oa.pre[m] + y : y;
-  t = t + oa.beta;
-  oa.out[m] = 1.0f / (1.0f + expf(-t));
+  oa.out[m] = out_head(oa, m, p);
 }
 
 int launch_tower_head(hipStream_t s, int M, int N, const float* h, int ldh, const OutArgs& oa) {

@@ -47,6 +47,34 @@ static __device__ __attribute__((aligned(16))) float g_rmx_zero16[4];
 // id -1 (a zero row): the LDS-DMA source of out-of-range entries of the id ring
 static __device__ __attribute__((aligned(16))) int g_rmx_neg1[4] = {-1, -1, -1, -1};
 
+// The head of every model (DeepFM.scala:54-80 and the other models: CAddTable + Sigmoid): the probability of a
+// row from y, its output dot.  ONE floating-point order, which every kernel that ends in a head applies:
+//   y + bo;  rs + .  (the CIN's row sum);  pre2 + .  (DCN's cross term);  pre + .  (y1 + y2, y1);  . + beta;  sigmoid
+__device__ __forceinline__ float out_sigmoid(float t) { return 1.0f / (1.0f + expf(-t)); }
+// This form takes the row's terms already loaded (k_tail.hip loads them a block early; the fused and the small
+// tower compute pre themselves); a term is added when its has_* is set.
+__device__ __forceinline__ float out_head(const OutArgs& oa, float y, bool has_rs, float rs, bool has_pre2, float pre2,
+                                          bool has_pre, float pre) {
+  if (oa.has_bo) y = y + oa.bo;
+  if (has_rs) y = rs + y;
+  if (has_pre2) y = pre2 + y;
+  const float t = has_pre ? pre + y : y;
+  return out_sigmoid(t + oa.beta);
+}
+// ... and this one loads row m's terms from oa, each where it is added: rowsum (summed in order), pre2, pre.
+// (Written out, not loaded first and passed to the form above: with its loads moved, the row-owner tail
+// (k_tail_s3.hip, 258 spilled SGPRs) was allocated differently from end to end.)
+__device__ __forceinline__ float out_head(const OutArgs& oa, int m, float y) {
+  if (oa.has_bo) y = y + oa.bo;
+  if (oa.rowsum) {
+    float rs = 0.f;
+    for (int jj = 0; jj < oa.rowsum_k; ++jj) rs += oa.rowsum[(int64_t)m * oa.rowsum_k + jj];
+    y = rs + y;
+  }
+  if (oa.pre2) y = oa.pre2[m] + y;
+  const float t = oa.pre ? oa.pre[m] + y : y;
+  return out_sigmoid(t + oa.beta);
+}
 
 // s_waitcnt vmcnt(n) for a wave-uniform runtime n (the immediate must be a constant)
 __device__ __forceinline__ void vm_wait(int n) {
@@ -1367,16 +1395,7 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
           oa.part[(int64_t)by * M + m] = y;
           continue;
         }
-        if (oa.has_bo) y = y + oa.bo;
-        if (oa.rowsum) {
-          float rs = 0.f;
-          for (int jj = 0; jj < oa.rowsum_k; ++jj) rs += oa.rowsum[(int64_t)m * oa.rowsum_k + jj];
-          y = rs + y;
-        }
-        if (oa.pre2) y = oa.pre2[m] + y;
-        float t = oa.pre ? oa.pre[m] + y : y;
-        t = t + oa.beta;
-        oa.out[m] = 1.0f / (1.0f + expf(-t));
+        oa.out[m] = out_head(oa, m, y);
       }
     }
     if constexpr (EPI == kEpiCin) {

@@ -150,22 +150,13 @@ int launch_dx_s3(hipStream_t s, const DenseLayer& L, int B, const float* dpre, i
 }
 
 // Output head of a layer computed in ny column slices: logit = sum of the slices' partial dots
-// (slice order), then the same combination as the fused epilogue (k_gemm.hpp kEpiOutput).
+// (slice order), then the head (k_gemm.hpp out_head), as the fused epilogue (kEpiOutput) applies it.
 __global__ __launch_bounds__(256) void out_finish_kernel(int M, int ny, OutArgs oa) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
   float y = oa.part[m];
   for (int j = 1; j < ny; ++j) y += oa.part[(int64_t)j * M + m];
-  if (oa.has_bo) y = y + oa.bo;
-  if (oa.rowsum) {
-    float rs = 0.f;
-    for (int jj = 0; jj < oa.rowsum_k; ++jj) rs += oa.rowsum[(int64_t)m * oa.rowsum_k + jj];
-    y = rs + y;
-  }
-  if (oa.pre2) y = oa.pre2[m] + y;
-  float t = oa.pre ? oa.pre[m] + y : y;
-  t = t + oa.beta;
-  oa.out[m] = 1.0f / (1.0f + expf(-t));
+  oa.out[m] = out_head(oa, m, y);
 }
 
 int launch_out_finish(hipStream_t s, int M, int ny, const OutArgs& oa) {
@@ -234,10 +225,7 @@ int launch_tower_s3(hipStream_t s, GemmArgs& p, int amode, Epi epi) {
   // order (bitwise).  DeepFM's layers on the engine at B = 4,096: 0.0486 / 0.0288 / 0.0270 ->
   // 0.0444 / 0.0265 / 0.0249 ms (profiles/r04/ab_small_rt.txt)
   if (tuning_get("s3_narrow", 1) != 0 && !s3_mt2(p.M, p.Npad, amode, p.ga.ids != nullptr)) {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      ncu = 256;
+    const int ncu = cu_count_or(256);
     const int64_t blocks8 = (int64_t)(p.M + 127) / 128 * (p.Npad / (kS3NT * 16));
     if (blocks8 < ncu) return launch_epi<Tile<1, kS3NT, 2, 1, 1, 2, 2>, kPrecS3>(s, p, amode, epi);
   }
@@ -284,10 +272,7 @@ int launch_cin_s3(hipStream_t s, GemmArgs& p) {
     // every CU does.  Same products in the same K order (bitwise).  xDeepFM at B = 1,024: CIN layers 2 / 3
     // 0.735 -> 0.301 ms, 0.61 -> 1.38 M examples/s; B = 2,048: 1.21 -> 1.99 M (profiles/r04/ab_cin_narrow.txt)
     if (tuning_get("cin_narrow", 1) != 0 && tuning_get("s3_stagger", 1) != 2) {
-      int dev = 0, ncu = 256;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        ncu = 256;
+      const int ncu = cu_count_or(256);
       const int64_t nslice = p.Npad / (kS3NT * 16);
       auto blocks = [&](int rows) { return (int64_t)(p.M + rows - 1) / rows * nslice; };
       if (blocks(256) < ncu) {

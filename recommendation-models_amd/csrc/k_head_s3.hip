@@ -28,22 +28,14 @@ namespace rmx {
 namespace {
 using namespace rowown;
 
-constexpr int kHMaxF = 40;                       // fields (K = 16 F <= 640, 20 K steps)
-constexpr int kHA = 2 * 2 * 16 * 64;             // per wave: 2 slots x [2 fields][16 samples][64 B]
-constexpr int kHId = 4 * 128;                    // per wave: 4 slots x [2 fields][16] ids
-constexpr int kHWr = 2 * 128;                    // per wave: 2 slots x [2 fields][16] first-order weights
-constexpr int kHWave = kHA + kHId + kHWr;
-constexpr size_t kHLds = (size_t)kQSlots * kQUnit + (size_t)kQW * kHWave + sizeof(float) * kQN;
+// LDS: the ring | per wave the gathered-A stream's slots (k_rowown.hpp kGWave) | b1
+constexpr size_t kHLds = (size_t)kQSlots * kQUnit + (size_t)kQW * kGWave + sizeof(float) * kQN;
 static_assert(kHLds <= 160 * 1024, "LDS budget");
 
 struct HeadS3Args {
   int M, F, KS;           // KS = ceil(F / 2) K steps
   QRows rows;             // full / half row blocks (k_rowown.hpp)
-  const int32_t* ids;     // [M][F]
-  const float* table;     // row of id at table + (id << gsh) (16 fp32: k = 16)
-  int gsh;
-  const float* wtab;      // first-order weight of id at wtab[id << wsh]
-  int wsh;
+  GatherArgs ga;          // ids [M][F], table, first-order weights (k_rowown.hpp)
   const bf16_t* W;        // [KS][3][416][32] split planes of Linear(16 F -> 400) (DenseLayer::W3)
   const float* b;         // [416]
   float* H;               // [M][416] out: ReLU(x W^T + b), columns 400 .. 415 zero
@@ -61,40 +53,7 @@ __device__ __attribute__((aligned(16))) float g_head_sink[64 * 4];
 
 // K step c, half h of unit u (wave-uniform)
 __device__ __forceinline__ const bf16_t* h_unit_src(const HeadS3Args& p, int u) {
-  const int c = u >> 1, half = u & 1;
-  return p.W + (int64_t)(c * 3 * kQN + half * kQUT * 16) * 32;
-}
-
-// ids of K step c of the row block at row0 (nw waves own rows) into id slot `slot` (lanes 0 .. 31: field
-// 2c + (L >> 4) of sample L & 15; past M or F, or for a wave without rows: -1)
-__device__ __forceinline__ void h_id_dma(const HeadS3Args& p, char* wl, int row0, int nw, int c, int slot, int w,
-                                         int lane) {
-  int f = lane >> 4, r = lane & 15;
-  asm volatile("" : "+v"(f), "+v"(r));
-  const int m = row0 + w * 16 + r, fld = 2 * c + f;
-  const bool ok = w < nw && m < p.M && fld < p.F;
-  const int32_t* src = ok ? p.ids + (int64_t)m * p.F + fld : g_rmx_neg1;
-  if (lane < 32)
-    lds_dma<4>(src, wl + kHA + slot * 128);
-}
-
-// rows (2 DMAs: field f = instruction, lane L: sample L >> 2, physical 16-B slot L & 3 = logical slot
-// swz_slot(sample, L & 3)) and first-order weights (lanes 0 .. 31) of the wave's step s, from the ids
-// in id slot s & 3, into A slot s & 1 / weight slot s & 1
-__device__ __forceinline__ void h_row_dma(const HeadS3Args& p, char* wl, int s, int lane) {
-  const int* ids = reinterpret_cast<const int*>(wl + kHA + (s & 3) * 128);
-  int r = lane >> 2, g = swz_slot(lane >> 2, lane & 3), lw = lane & 31;
-  asm volatile("" : "+v"(r), "+v"(g), "+v"(lw));
-  const int id0 = ids[r], id1 = ids[16 + r], idw = ids[lw];
-  const float* zero16 = g_rmx_zero16;
-  const float* s0 = id0 >= 0 ? p.table + ((int64_t)id0 << p.gsh) + 4 * g : zero16;
-  const float* s1 = id1 >= 0 ? p.table + ((int64_t)id1 << p.gsh) + 4 * g : zero16;
-  const float* sw = idw >= 0 ? p.wtab + ((int64_t)idw << p.wsh) : zero16;
-  char* a = wl + (s & 1) * 2048;
-  lds_dma<16>(s0, a);
-  lds_dma<16>(s1, a + 1024);
-  if (lane < 32)
-    lds_dma<4>(sw, wl + kHA + kHId + (s & 1) * 128);
+  return q_plane_src(p.W, u >> 1, u & 1);
 }
 
 // XS (training forward, k_head_s3 as DeepFM's layer 1 + encoder): also x and the FM sums, from the rows the
@@ -106,37 +65,26 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_head_s3_kernel(HeadS3Args 
   char* lds = hsmem;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r16 = lane & 15;
-  char* wl = hsmem + kQSlots * kQUnit + w * kHWave;  // this wave's rows / ids / weights
-  float* bl = reinterpret_cast<float*>(hsmem + kQSlots * kQUnit + kQW * kHWave);
+  char* wl = hsmem + kQSlots * kQUnit + w * kGWave;  // this wave's rows / ids / weights
+  float* bl = reinterpret_cast<float*>(hsmem + kQSlots * kQUnit + kQW * kGWave);
   const int nit = p.rows.nit(blockIdx.x);
   const int KS = p.KS, NU = 2 * KS;  // units per row block
 
   for (int i = tid; i < kQN; i += kQThreads) bl[i] = p.b ? p.b[i] : 0.f;
-  int lo = (lane >> 2) * 32 + swz_slot(lane >> 2, lane & 3) * 8;
-  asm volatile("" : "+v"(lo));
+  Q_LANE_LO(lo, lane);
   const int fb = q_fbase(lane);
 
-  // the wave's steps s = 0, 1, ... run over its row blocks: step s is K step s % KS of row block
-  // blockIdx.x + (s / KS) gridDim.x (none past the last); its ring slots are s & 3 (ids) and s & 1
-  auto id_dma = [&](int s) {
-    const int it = s / KS, c = s - it * KS;
-    int row0, nw;
-    p.rows.desc(blockIdx.x, it, row0, nw);
-    h_id_dma(p, wl, row0, nw, c, s & 3, w, lane);
-  };
+  // the wave's steps s = 0, 1, ... of the gathered-A stream run on over its row blocks (k_rowown.hpp)
+  auto id_dma = [&](int s) { g_id_dma_step(p.ga.ids, p.M, p.F, p.rows, KS, wl, s, w, lane); };
   if (nit > 0) {
-    for (int s = 0; s < 3; ++s) id_dma(s);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    h_row_dma(p, wl, 0, lane);
+    for (int i = 0; i < 3; ++i) id_dma(i);
+    q_drain();
+    g_row_dma(p.ga, wl, 0, lane);
     const bf16_t* s0 = h_unit_src(p, 0);
     const bf16_t* s1 = h_unit_src(p, 1);
-#pragma unroll
-    for (int qq = 0; qq < kQQ; ++qq) q_dma(s0, lds, 0, w, qq, lo);
-#pragma unroll
-    for (int qq = 0; qq < kQQ; ++qq) q_dma(s1, lds, 1, w, qq, lo);
+    Q_PROLOGUE(s0, s1, lds, w, lo);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  q_meet();
 
   int slot = 0, s = 0;
   for (int it = 0; it < nit; ++it) {
@@ -149,14 +97,14 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_head_s3_kernel(HeadS3Args 
       for (int c = 0; c < KS; ++c, ++s) {
         q_enter<5>();
         id_dma(s + 3);
-        h_row_dma(p, wl, s + 1, lane);
+        g_row_dma(p.ga, wl, s + 1, lane);
         __builtin_amdgcn_sched_barrier(0);
         const int u = 2 * c;
-        int dslot = slot == 0 ? 2 : slot - 1;
+        int dslot = q_dslot(slot);
         q_dma_only(h_unit_src(p, u + 2 < NU ? u + 2 : u + 2 - NU), lds, dslot, w, lo);
         slot = q_next(slot);
         q_enter<9>();
-        dslot = slot == 0 ? 2 : slot - 1;
+        dslot = q_dslot(slot);
         q_dma_only(h_unit_src(p, u + 3 < NU ? u + 3 : u + 3 - NU), lds, dslot, w, lo);
         slot = q_next(slot);
       }
@@ -179,7 +127,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_head_s3_kernel(HeadS3Args 
         const char* a = wl + (s & 1) * 2048;
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(a + o);
         const f32x4 a1 = *reinterpret_cast<const f32x4*>(a + 1024 + o);
-        const float* wr = reinterpret_cast<const float*>(wl + kHA + kHId + (s & 1) * 128);
+        const float* wr = reinterpret_cast<const float*>(wl + kGA + kGId + (s & 1) * 128);
         {
 #pragma clang fp contract(off)
           fm_accum(a0, a1, fs, fq);  // (SecondOrderEncoder sums, field order, k_gemm.hpp)
@@ -193,7 +141,7 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_head_s3_kernel(HeadS3Args 
       // ids three steps ahead (their slot held step s - 1's, read at step s - 2); rows + weights of the
       // next step into the A / weight slots step s - 1 used (its ids landed: issued at step s - 2)
       id_dma(s + 3);
-      h_row_dma(p, wl, s + 1, lane);
+      g_row_dma(p.ga, wl, s + 1, lane);
       if constexpr (XS) {
         const int mx = row0 + w * 16 + r16, f0 = 2 * c;
         const bool okm = mx < p.M;
@@ -206,12 +154,12 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_head_s3_kernel(HeadS3Args 
       }
       __builtin_amdgcn_sched_barrier(0);  // these 4 (XS: 6) ahead of the unit's 5 (the static vmcnt counts)
       const int u = 2 * c;
-      int dslot = slot == 0 ? 2 : slot - 1;
+      int dslot = q_dslot(slot);
       q_unit<kQUT, 0>(lds + slot * kQUnit, fb, ah, am, al, acc, h_unit_src(p, u + 2 < NU ? u + 2 : u + 2 - NU), lds,
                       dslot, w, lo);
       slot = q_next(slot);
       q_enter<XS ? 11 : 9>();  // previous unit: 1 id + 2 row + 1 weight (+ 2 x stores) + 5 plane DMAs
-      dslot = slot == 0 ? 2 : slot - 1;
+      dslot = q_dslot(slot);
       q_unit<kQNT - kQUT, kQUT>(lds + slot * kQUnit, fb, ah, am, al, acc,
                                 h_unit_src(p, u + 3 < NU ? u + 3 : u + 3 - NU), lds, dslot, w, lo);
       slot = q_next(slot);
@@ -256,62 +204,55 @@ __global__ __launch_bounds__(kQThreads, 1) void tower_head_s3_kernel(HeadS3Args 
     if constexpr (XS)
       if (p.S && m < p.M) *reinterpret_cast<f32x4*>(p.S + (int64_t)m * 16 + g4) = fs;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing DMAs land before the LDS is released
+  q_drain();
 }
 
 }  // namespace
 
+// the shapes the kernel takes: a k = 16 gather by ids (F <= 40) into a 400-wide split-GEMM layer
+static bool head_s3_shape(const DenseLayer& L1, int M, int F, int k, bool ids) {
+  if (M <= 0 || !ids || k != 16 || F < 1 || F > kGMaxF || !L1.W3 || L1.W16 || !f32_split_enabled()) return false;
+  return L1.K == 16 * F && L1.N == 400 && L1.Npad == kQN && L1.N1 < 0 && L1.bias_mode == 1 && L1.K1 < 0;
+}
+
 bool tower_head_s3_usable(const DenseLayer& L1, int M, int F, int k, bool ids) {
-  if (M <= 0 || !ids || k != 16 || F < 1 || F > kHMaxF || !L1.W3 || L1.W16 || !f32_split_enabled()) return false;
-  if (!(L1.K == 16 * F && L1.N == 400 && L1.Npad == kQN && L1.N1 < 0 && L1.bias_mode == 1 && L1.K1 < 0)) return false;
   // knob "s3_head": 0 off, 2 always, 1 (default) when the (half) row blocks fill every CU at least once
   // (default 1 since measured: DeepFM B = 65,536 186.0 -> 188.2 M examples/s, layer 1 0.182 -> 0.173 ms,
   // profiles/r04/ab_round4_first.txt)
-  const int knob = tuning_get("s3_head", 1);
-  if (knob == 0) return false;
-  if (knob == 2) return true;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    ncu = 256;
-  // (half) row blocks that fill every CU, or -- with half blocks -- any batch above the whole-tower kernel's
-  // one round (k_small_s3.hip: M <= 16 ncu): half blocks on part of the chip still beat three engine launches
-  return q_fills(M, ncu) || (tuning_get("half_blocks", 1) != 0 && M > 16 * ncu);
+  return head_s3_shape(L1, M, F, k, ids) && q_auto("s3_head", M);
 }
 
 int launch_tower_head_s3(hipStream_t s, const DenseLayer& L1, int M, int F, const int32_t* ids, const float* table,
                          int ld, const float* wtab, int wld, float* H, int ldc, float* fm_y, int fm_sums, float* X,
                          int ldx, float* S) {
+  // (as it always was: with the knob at 2 the launch takes the caller's word for the shape; only the auto
+  // choice is refused here)
   if (!tower_head_s3_usable(L1, M, F, 16, ids != nullptr) && tuning_get("s3_head", 1) != 2) {
     set_error("fp32 tower head: needs a k = 16 gather (F <= 40, ids) into a 400-wide split-GEMM layer");
     return RMX_E_INVALID;
   }
   if (M <= 0) return RMX_OK;
-  const int l = ld > 0 ? ld : 16, wl = wld > 0 ? wld : 1;
-  if ((l & (l - 1)) || l < 16 || (wl & (wl - 1)) || ldc != kQN || !H) {
+  HeadS3Args p{};
+  if (!gather_shifts(ld, wld, p.ga.gsh, p.ga.wsh) || ldc != kQN || !H) {
     set_error("fp32 tower head: table / weight strides must be powers of two, h1 [M][416]");
     return RMX_E_INVALID;
   }
-  int dev = 0, ncu = 0;
-  RMX_HIP(hipGetDevice(&dev));
-  RMX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  int ncu = 0;
+  RMX_HIP(cu_count(&ncu));
   if (X && ldx < 16 * F) {
     set_error("fp32 tower head: x needs ldx >= 16 F");
     return RMX_E_INVALID;
   }
   const void* fn = X ? (const void*)tower_head_s3_kernel<true> : (const void*)tower_head_s3_kernel<false>;
   RMX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHLds));
-  HeadS3Args p{};
   p.M = M;
   int grid = 0;
   p.rows = q_rows(M, ncu, grid);
   p.F = F;
   p.KS = (F + 1) / 2;
-  p.ids = ids;
-  p.table = table;
-  p.gsh = __builtin_ctz((unsigned)l);
-  p.wtab = wtab;
-  p.wsh = __builtin_ctz((unsigned)wl);
+  p.ga.ids = ids;
+  p.ga.table = table;
+  p.ga.wtab = wtab;
   p.W = L1.W3;
   p.b = L1.b;
   p.H = H;

@@ -24,13 +24,12 @@ namespace rmx {
 namespace {
 using namespace rowown;
 
-constexpr int kLKS = 13;                    // 32-wide K steps (K = 400, Kpad 416)
+constexpr int kLKS = kQAKS;                 // 32-wide K steps (K = 400, Kpad 416)
 constexpr int kLUnits = 2 * kLKS;           // units per row block
-constexpr int kLH = kQW * 2 * 2048;         // A: two 2-KiB step slots per wave
+constexpr int kLH = kQW * kQAWave;          // A: two 2-KiB step slots per wave (k_rowown.hpp a_dma)
 constexpr size_t kLLds = (size_t)kQSlots * kQUnit + kLH + sizeof(float) * kQN;
 static_assert(kLLds <= 160 * 1024, "LDS budget");
 
-__device__ __attribute__((aligned(16))) float g_lzero_row[kQN];   // A / mask rows past M
 __device__ __attribute__((aligned(16))) float g_lsink[64 * 4];     // stores of rows past M
 
 struct LayerS3Args {
@@ -47,32 +46,7 @@ struct LayerS3Args {
 };
 
 __device__ __forceinline__ const bf16_t* l_unit_src(const LayerS3Args& p, int u) {
-  const int c = u >> 1, half = u & 1;
-  return p.W + (int64_t)(c * 3 * kQN + half * kQUT * 16) * 32;
-}
-
-// A of K step c of the row block at row0 into this wave's slot ds (k_tail_s3.hip q_h1_dma)
-__device__ __forceinline__ void l_a_dma(const LayerS3Args& p, const float* zrow, char* alds, int row0, int nw, int c,
-                                        int ds, int w, int lane) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int r = 8 * i + (lane >> 3), j = (lane & 7) ^ ((lane >> 3) & 7);
-    asm volatile("" : "+v"(r), "+v"(j));
-    const int m = row0 + w * 16 + r;
-    const uint32_t ok = (w < nw && m < p.M) ? 1u : 0u;
-    const uintptr_t base = (uintptr_t)zrow + (uintptr_t)ok * ((uintptr_t)p.A - (uintptr_t)zrow);
-    const float* row = reinterpret_cast<const float*>(base) + (uint32_t)(m * (int)ok) * (uint32_t)p.lda;
-    lds_dma<16>(row + 32 * c + 4 * j, alds + ds * 2048 + i * 1024);
-  }
-}
-
-__device__ __forceinline__ void l_a_read(const char* alds, int c, int lane, f32x4& a0, f32x4& a1) {
-  const int r = lane & 15, g = lane >> 4;
-  int o0 = r * 128 + ((g ^ (r & 7)) << 4), o1 = r * 128 + (((g + 4) ^ (r & 7)) << 4);
-  asm volatile("" : "+v"(o0), "+v"(o1));
-  a0 = *reinterpret_cast<const f32x4*>(alds + (c & 1) * 2048 + o0);
-  a1 = *reinterpret_cast<const f32x4*>(alds + (c & 1) * 2048 + o1);
-  if (c == kLKS - 1) a1 = f32x4{0.f, 0.f, 0.f, 0.f};
+  return q_plane_src(p.W, u >> 1, u & 1);
 }
 
 // vector-memory instructions of the epilogue, counted by the next block's first waits: EPI 0 26 row stores
@@ -86,7 +60,7 @@ __global__ __launch_bounds__(kQThreads, 1) void layer_s3_kernel(LayerS3Args p) {
   extern __shared__ __attribute__((aligned(16))) char lsmem[];
   char* lds = lsmem;
   float* bl = reinterpret_cast<float*>(lsmem + kQSlots * kQUnit + kLH);
-  const float* zrow = g_lzero_row;
+  const float* zrow = g_qzero_row;  // A / mask rows past M
   asm volatile("" : "+s"(zrow));
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, r16 = lane & 15;
@@ -94,23 +68,16 @@ __global__ __launch_bounds__(kQThreads, 1) void layer_s3_kernel(LayerS3Args p) {
 
   if (EPI == 0)
     for (int i = tid; i < kQN; i += kQThreads) bl[i] = p.b ? p.b[i] : 0.f;
-  int lo = (lane >> 2) * 32 + swz_slot(lane >> 2, lane & 3) * 8;
-  asm volatile("" : "+v"(lo));
+  Q_LANE_LO(lo, lane);
   const int fb = q_fbase(lane);
   char* alds = lsmem + kQSlots * kQUnit + w * 4096;
   {
     int row0, nw;
     p.rows.desc(blockIdx.x, 0, row0, nw);
-    l_a_dma(p, zrow, alds, row0, nw, 0, 0, w, lane);
+    a_dma(p.A, p.lda, p.M, zrow, alds, row0, nw, 0, 0, w, lane);
   }
-  if (nit > 0) {
-#pragma unroll
-    for (int q = 0; q < kQQ; ++q) q_dma(l_unit_src(p, 0), lds, 0, w, q, lo);
-#pragma unroll
-    for (int q = 0; q < kQQ; ++q) q_dma(l_unit_src(p, 1), lds, 1, w, q, lo);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  if (nit > 0) Q_PROLOGUE(l_unit_src(p, 0), l_unit_src(p, 1), lds, w, lo);
+  q_meet();
 
   int slot = 0;
   for (int it = 0; it < nit; ++it) {
@@ -123,15 +90,15 @@ __global__ __launch_bounds__(kQThreads, 1) void layer_s3_kernel(LayerS3Args p) {
       for (int c = 0; c < kLKS; ++c) {
         q_enter<5>();
         if (c + 1 < kLKS)
-          l_a_dma(p, zrow, alds, row0, nw, c + 1, (c + 1) & 1, w, lane);
+          a_dma(p.A, p.lda, p.M, zrow, alds, row0, nw, c + 1, (c + 1) & 1, w, lane);
         else
-          l_a_dma(p, zrow, alds, row0n, nwn, 0, 0, w, lane);
+          a_dma(p.A, p.lda, p.M, zrow, alds, row0n, nwn, 0, 0, w, lane);
         __builtin_amdgcn_sched_barrier(0);
-        int dslot = slot == 0 ? 2 : slot - 1;
+        int dslot = q_dslot(slot);
         q_dma_only(l_unit_src(p, (2 * c + 2) % kLUnits), lds, dslot, w, lo);
         slot = q_next(slot);
         q_enter<7>();
-        dslot = slot == 0 ? 2 : slot - 1;
+        dslot = q_dslot(slot);
         q_dma_only(l_unit_src(p, (2 * c + 3) % kLUnits), lds, dslot, w, lo);
         slot = q_next(slot);
       }
@@ -150,21 +117,21 @@ __global__ __launch_bounds__(kQThreads, 1) void layer_s3_kernel(LayerS3Args p) {
       bf16x8 ah, am, al;
       {
         f32x4 a0, a1;
-        l_a_read(alds, c, lane, a0, a1);
+        a_read(alds, c, lane, a0, a1, kLKS - 1);
         split3(a0, a1, ah, am, al);
       }
       // the next step's A, or the next row block's step 0 into the slot just read (step 12 is slot 0)
       if (c + 1 < kLKS)
-        l_a_dma(p, zrow, alds, row0, nw, c + 1, (c + 1) & 1, w, lane);
+        a_dma(p.A, p.lda, p.M, zrow, alds, row0, nw, c + 1, (c + 1) & 1, w, lane);
       else
-        l_a_dma(p, zrow, alds, row0n, nwn, 0, 0, w, lane);
+        a_dma(p.A, p.lda, p.M, zrow, alds, row0n, nwn, 0, 0, w, lane);
       __builtin_amdgcn_sched_barrier(0);
       const int u = 2 * c;
-      int dslot = slot == 0 ? 2 : slot - 1;
+      int dslot = q_dslot(slot);
       q_unit<kQUT, 0>(lds + slot * kQUnit, fb, ah, am, al, acc, l_unit_src(p, (u + 2) % kLUnits), lds, dslot, w, lo);
       slot = q_next(slot);
       q_enter<7>();  // previous unit: 2 A loads + 5 DMAs
-      dslot = slot == 0 ? 2 : slot - 1;
+      dslot = q_dslot(slot);
       q_unit<kQNT - kQUT, kQUT>(lds + slot * kQUnit, fb, ah, am, al, acc, l_unit_src(p, (u + 3) % kLUnits), lds, dslot,
                                 w, lo);
       slot = q_next(slot);
@@ -212,7 +179,7 @@ __global__ __launch_bounds__(kQThreads, 1) void layer_s3_kernel(LayerS3Args p) {
     }
     crow[cstep * kQNT] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  q_drain();
 }
 
 }  // namespace
@@ -227,10 +194,7 @@ bool layer_s3_usable(const DenseLayer& L, bool dx, int M, int lda, int ldc) {
         ldc >= kQN && ldc % 4 == 0))
     return false;
   if (dx ? (L.NTpad != kQN || (L.KTpad / 16 + 1) / 2 != kLKS) : (L.Kpad + 31) / 32 != kLKS) return false;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    ncu = 256;
+  const int ncu = cu_count_or(256);
   return q_fills(M, ncu) && (int64_t)M * lda < ((int64_t)1 << 31);
 }
 
@@ -240,9 +204,8 @@ int launch_layer_s3(hipStream_t s, const DenseLayer& L, bool dx, int M, const fl
     set_error("fp32 row-owner layer: needs a 400 x 400 split-GEMM layer, [M][>= 416] operands and a full round of row blocks");
     return RMX_E_INVALID;
   }
-  int dev = 0, ncu = 0;
-  RMX_HIP(hipGetDevice(&dev));
-  RMX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  int ncu = 0;
+  RMX_HIP(cu_count(&ncu));
   LayerS3Args p{};
   p.M = M;
   int grid = 0;

@@ -321,10 +321,7 @@ __device__ void s_wave(const SmallArgs& p, float* ssmem, int tid, int w, int lan
 #pragma unroll
       for (int q = 1; q < kSW; ++q) y += red[q * kSR + tid];
       const OutArgs& oa = p.oa;
-      if (oa.has_bo) y = y + oa.bo;
-      float t = fmv[tid] + y;  // pre (first order + FM) + the tower's logit, out_finish_kernel's order
-      t = t + oa.beta;
-      oa.out[m] = 1.0f / (1.0f + expf(-t));
+      oa.out[m] = out_head(oa, y, false, 0.f, false, 0.f, true, fmv[tid]);  // pre: first order + FM
     }
   }
 }
@@ -355,10 +352,7 @@ bool tower_small_s3_usable(const rmx_model& m, int M, int F, int k, bool ids) {
   const int knob = tuning_get("s3_small", 1);
   if (knob == 0) return false;
   if (knob == 2) return true;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    ncu = 256;
+  const int ncu = cu_count_or(256);
   // one round of 16- or 32-sample blocks (B <= 8,192 on 256 CUs): every block streams all three layers'
   // weights, so a second round costs a whole round again (B = 16,384: 53 M examples/s, against ~156 M on
   // the row-owner head + tail's half blocks, profiles/r04/grid_summary.txt)
@@ -368,8 +362,8 @@ bool tower_small_s3_usable(const rmx_model& m, int M, int F, int k, bool ids) {
 int launch_tower_small_s3(hipStream_t s, const rmx_model& m, int M, int F, const int32_t* ids, const float* table,
                           int ld, const float* wtab, int wld, const OutArgs& oa) {
   if (M <= 0) return RMX_OK;
-  const int l = ld > 0 ? ld : 16, wl = wld > 0 ? wld : 1;
-  if ((l & (l - 1)) || l < 16 || (wl & (wl - 1)) || !oa.wo || !oa.out) {
+  SmallArgs p{};
+  if (!gather_shifts(ld, wld, p.gsh, p.wsh) || !oa.wo || !oa.out) {
     set_error("fp32 small tower: table / weight strides must be powers of two, and an output head");
     return RMX_E_INVALID;
   }
@@ -380,20 +374,14 @@ int launch_tower_small_s3(hipStream_t s, const rmx_model& m, int M, int F, const
   // 0.071 ms (profiles/r04/ab_small_rt.txt)
   int rt = tuning_get("s3_small_rt", 0);
   if (rt != 1 && rt != 2) {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      ncu = 256;
+    const int ncu = cu_count_or(256);
     rt = M <= 16 * ncu ? 1 : 2;
   }
-  SmallArgs p{};
   p.M = M;
   p.F = F;
   p.ids = ids;
   p.table = table;
-  p.gsh = __builtin_ctz((unsigned)l);
   p.wtab = wtab;
-  p.wsh = __builtin_ctz((unsigned)wl);
   for (int i = 0; i < 3; ++i) {
     p.W[i] = m.layers[i].W3;
     p.b[i] = m.layers[i].b;

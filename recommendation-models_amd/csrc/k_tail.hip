@@ -426,11 +426,8 @@ __global__ __launch_bounds__(kTThreads, 1) void tower_tail_bf16_kernel(TailArgs 
         float y = red[hrow];
 #pragma unroll
         for (int q = 1; q < kTCW; ++q) y += red[q * kTBM + hrow];
-        if (oa.has_bo) y = y + oa.bo;
-        if (oa.rowsum || oa.pre2) y = in2 + y;
-        float t = has_pre ? pr + y : y;
-        t = t + oa.beta;
-        oa.out[m] = 1.0f / (1.0f + expf(-t));
+        // (in2 is the row sum or pre2, never both: one term)
+        oa.out[m] = out_head(oa, y, oa.rowsum || oa.pre2, in2, false, 0.f, has_pre, pr);
       }
     };
     for (int it = 0; it < nit; ++it) {
@@ -500,9 +497,8 @@ int launch_tower_tail_bf16(hipStream_t s, const DenseLayer& L2, const DenseLayer
     set_error("tower tail: needs two bf16 layers of N <= 400 (Npad = Kpad = 416) and an output head");
     return RMX_E_INVALID;
   }
-  int dev = 0, ncu = 0;
-  RMX_HIP(hipGetDevice(&dev));
-  RMX_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  int ncu = 0;
+  RMX_HIP(cu_count(&ncu));
   RMX_HIP(hipFuncSetAttribute((const void*)tower_tail_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)kTLds));
   TailArgs p{};

@@ -639,6 +639,18 @@ void table_inputs(const rmx_table& t, const rmx_model& m, FwdInputs& in) {
 }
 
 // The per-model kernel sequence.  in.ids == nullptr means implicit ids (L-A gathered rows).
+// the head's arguments that every path takes from the model and the call: the output Linear, the global bias
+// and where the probabilities go (a path adds its own pre / pre2 / rowsum / part)
+static OutArgs model_out_args(const rmx_model& m, const FwdInputs& in) {
+  OutArgs oa{};
+  oa.wo = m.wo;
+  oa.bo = m.bo;
+  oa.has_bo = m.has_bo ? 1 : 0;
+  oa.beta = in.beta;
+  oa.out = in.out;
+  return oa;
+}
+
 int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
   const int B = in.B;
   if (B == 0) return RMX_OK;
@@ -681,13 +693,8 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
                                in.wld, in.ids ? m.xbuf : nullptr)))
         return st;
     }
-    OutArgs oa{};
-    oa.wo = m.wo;
-    oa.bo = m.bo;
-    oa.has_bo = m.has_bo ? 1 : 0;
+    OutArgs oa = model_out_args(m, in);
     oa.pre = m.ws.y12;
-    oa.beta = in.beta;
-    oa.out = in.out;
     oa.part = m.ws.opart;
     const float* A = in.ids ? m.xbuf : (const float*)in.table;
     int lda = F * k;
@@ -712,12 +719,7 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
   if (m.type == RMX_MODEL_DEEPFM && !in.y1 && in.dtype == kF32 && !needs_gather_x(m) &&
       tower_small_s3_usable(m, B, F, k, true)) {
     StageTimer t(m, s, "tower_small");
-    OutArgs oa{};
-    oa.wo = m.wo;
-    oa.bo = m.bo;
-    oa.has_bo = m.has_bo ? 1 : 0;
-    oa.beta = in.beta;
-    oa.out = in.out;
+    const OutArgs oa = model_out_args(m, in);
     return launch_tower_small_s3(s, m, B, F, in.ids, (const float*)in.table, in.ld, (const float*)in.wtab, in.wld, oa);
   }
 
@@ -726,12 +728,7 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
   if (m.type == RMX_MODEL_DEEPFM && in.ids && !in.y1 && in.dtype == kF32 && !needs_gather_x(m) && k == 16 &&
       m.layers.size() == 3 && tower_fused_s3_usable(m.layers[0], m.layers[1], m.layers[2], B, F, k, true)) {
     StageTimer t(m, s, "tower_fused");
-    OutArgs oa{};
-    oa.wo = m.wo;
-    oa.bo = m.bo;
-    oa.has_bo = m.has_bo ? 1 : 0;
-    oa.beta = in.beta;
-    oa.out = in.out;
+    const OutArgs oa = model_out_args(m, in);
     return launch_tower_fused_s3(s, m.layers[0], m.layers[1], m.layers[2], B, F, in.ids, (const float*)in.table, in.ld,
                                  (const float*)in.wtab, in.wld, oa);
   }
@@ -789,13 +786,8 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
   if (st) return st;
 
   // 2. interaction encoders
-  OutArgs oa{};
-  oa.wo = m.wo;
-  oa.bo = m.bo;
-  oa.has_bo = m.has_bo ? 1 : 0;
+  OutArgs oa = model_out_args(m, in);
   oa.pre = pre;
-  oa.beta = in.beta;
-  oa.out = in.out;
   oa.part = m.ws.opart;
   const float* A = nullptr;
   int lda = 0;

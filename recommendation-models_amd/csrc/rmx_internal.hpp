@@ -42,6 +42,28 @@ int tuning_get(const char* key, int def);  // rmx_set_tuning knobs (capi.hip)
     }                                                                              \
   } while (0)
 
+// The CU count of the current device.  A launch that sizes its grid by it fails on a failed query
+// (RMX_HIP(cu_count(&ncu))); a path choice falls back to the MI355X's 256 (cu_count_or(256)).
+inline hipError_t cu_count(int* ncu) {
+  int dev = 0;
+  const hipError_t e = hipGetDevice(&dev);
+  return e != hipSuccess ? e : hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev);
+}
+inline int cu_count_or(int def) {
+  int ncu = def;
+  return cu_count(&ncu) == hipSuccess ? ncu : def;
+}
+
+// The row strides of a k = 16 gather as shifts: table rows of ld elements (0 = 16) and first-order weights wld
+// apart (0 = 1), both powers of two, ld >= 16 (the kernels form id << shift).  false: not such strides.
+inline bool gather_shifts(int ld, int wld, int& gsh, int& wsh) {
+  const int l = ld > 0 ? ld : 16, wl = wld > 0 ? wld : 1;
+  if ((l & (l - 1)) || l < 16 || (wl & (wl - 1))) return false;
+  gsh = __builtin_ctz((unsigned)l);
+  wsh = __builtin_ctz((unsigned)wl);
+  return true;
+}
+
 // ---------------------------------------------------------------- layers ----
 // A BigDL Linear(in = K, out = N) packed for the fp32 MFMA GEMM:
 //   W chunked as [Kpad/16][Npad][16] (each 16-wide K chunk of all N rows contiguous),
