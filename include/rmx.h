@@ -449,13 +449,71 @@ int rmx_backward_pulled(rmx_model* m, rmx_shard* sh, int32_t batch, int slot, co
  * rmx_train_step_ids with a sharded optimiser, and rmx_train_step_sharded with a table's optimiser or another
  * shard's, fail with RMX_E_INVALID before any device call.
  * Out of scope: bf16, pre-aggregating per distinct id before the send (another summation order), a
- * fixed-capacity sync-free push, a host upload into a shard.  The RCCL transport at nranks > 1 has not been
+ * fixed-capacity sync-free push.  The RCCL transport at nranks > 1 has not been
  * executed for the push either (it uses the pull's grouped send / recv only). */
 int rmx_optim_create_sharded(rmx_model* m, rmx_shard* sh, int kind, const double* hyper, int n_hyper,
                              rmx_optim** out);
 int rmx_optim_shard_state_ptrs(const rmx_optim* o, int part, int slot, void** d_weights, void** d_embedding);
 int rmx_train_step_sharded(rmx_model* m, rmx_shard* sh, rmx_optim* o, int32_t batch, const int32_t* d_ids,
                            const float* d_targets, float* loss, void* stream);
+
+/* ------------------------------------------- loading and saving parameters ---- */
+/* Host ranges of rows into and out of a table, a shard and an optimiser's state: what a checkpoint, a warm start
+ * or a real model's load needs (csrc/param_io.hip).
+ * Host range convention (every call below): the host pointers address the first element of the id range
+ * [id0, id0 + n).  RMX_LAYOUT_ROW_MAJOR: embedding[i*k + j], ld ignored.  RMX_LAYOUT_K_MAJOR: embedding[j*ld + i]
+ * with ld >= n (ld = V and id0 = 0: the Angel PS matrix).  weights[i] is the first-order weight of row id0 + i.
+ * weights and embedding may each be NULL: that part is left as it is.  n = 0 returns RMX_OK without a device call.
+ * Every call first waits for earlier device work (a device synchronise: these are not per-batch calls) and is
+ * synchronous on return.  A range streams in chunks of "io_chunk_rows" rows (rmx_set_tuning; default 262,144)
+ * through two pinned host buffers and two device chunk buffers owned by the table or shard -- allocated at the
+ * first call, sized by the knob and k only (never by V), counted by rmx_debug_live_device_memory, reused by later
+ * calls and freed with the object; chunk c + 1's host copy and transfer are ordered so that they can run under chunk c's kernel.  Knob "io_nt" 1:
+ * non-temporal stores in the scatter (default 0).  Both defaults from the A/Bs of DESIGN.md §13: the calls reach
+ * 0.4-0.55 of a plain copy of the same bytes, bounded by the host copy into the pinned chunk.
+ * Errors: NULL handle, n < 0, an unknown layout, K_MAJOR with ld < n: RMX_E_INVALID; id0 < 0 or id0 + n > V:
+ * RMX_E_INDEX; every check runs before any device call and rmx_last_error names the argument.
+ *
+ * Replicated table (fp32 or bf16: an upload rounds to nearest even exactly as rmx_table_upload does, a download
+ * widens exactly).  An upload also writes the touched rows of the line copy (knob "table_lines"). */
+int rmx_table_upload_rows(rmx_table* t, int64_t id0, int64_t n, const float* weights, const float* embedding,
+                          int layout, int64_t ld);
+int rmx_table_download_rows(const rmx_table* t, int64_t id0, int64_t n, float* weights, float* embedding,
+                            int layout, int64_t ld);
+/* Sharded table.  LOCAL calls, not collective: a row is kept (upload) or returned (download) only when its owner
+ * partition lives in this shard object -- every partition of a loopback shard, else `rank`'s; owner = p(id) mod
+ * nranks, local row = p(id) div nranks under the shard's owner function.  Other rows are skipped on upload
+ * (*stored, nullable: the rows kept); on download their host elements are NOT written, owned[i] (nullable) says
+ * which rows were and *found (nullable) counts them.  So every rank may be handed the whole table and keeps its
+ * share (a loader that pre-partitions with rmx_owner_hash hands each rank less), at any nranks, without RCCL.
+ * An upload fixes the owner function as a fill does (rmx_shard_set_owner_hash is refused afterwards).  A row
+ * never uploaded reads as zeros; a line's pad floats and the partition's extra zero row stay zero.  Both calls
+ * return RMX_E_INVALID while a pull slot holds an unconsumed pull (a direct slot reads the partition in place). */
+int rmx_shard_upload_rows(rmx_shard* sh, int64_t id0, int64_t n, const float* weights, const float* embedding,
+                          int layout, int64_t ld, int64_t* stored);
+int rmx_shard_download_rows(rmx_shard* sh, int64_t id0, int64_t n, float* weights, float* embedding,
+                            int layout, int64_t ld, uint8_t* owned /* [n], nullable */, int64_t* found);
+/* Optimiser state, of a table's optimiser or a shard's (ownership as above; for a table every row is owned).
+ * slot 0: v / s / m, slot 1: Adam's v.  A slot the kind does not have (slot 1 of Momentum, any slot of SGD), the
+ * embedding state of LR and the first-order state of DNN: RMX_E_INVALID.  _dense: the [mats_len] and [1] state of
+ * mats and the bias (each nullable).  rmx_optim_set_steps: the step count t >= 0 (the next apply uses t + 1).
+ * With the rows, mats and bias restored too, a resumed run repeats the uninterrupted one bit for bit. */
+int rmx_optim_state_upload_rows(rmx_optim* o, int slot, int64_t id0, int64_t n, const float* weights,
+                                const float* embedding, int layout, int64_t ld, int64_t* stored);
+int rmx_optim_state_download_rows(rmx_optim* o, int slot, int64_t id0, int64_t n, float* weights, float* embedding,
+                                  int layout, int64_t ld, uint8_t* owned, int64_t* found);
+int rmx_optim_state_upload_dense(rmx_optim* o, int slot, const float* mats /* [mats_len] */, const float* bias);
+int rmx_optim_state_download_dense(rmx_optim* o, int slot, float* mats, float* bias);
+int rmx_optim_set_steps(rmx_optim* o, int64_t t);
+/* Test / bench hooks: the gather and the scatter kernel alone.  Rows [id0, id0 + n) (n > 0, at most one chunk of
+ * "io_chunk_rows") are gathered into a device chunk, then `iters` gathers and `iters` scatters of that chunk are
+ * timed by events: *get_ms / *put_ms (each nullable) = ms per launch.  The scatters store what the rows already
+ * hold, so the table or shard is unchanged.  layout: the chunk's form on the device (K_MAJOR: transposed through
+ * LDS).  Checks as the row calls. */
+int rmx_debug_table_row_kernels(rmx_table* t, int64_t id0, int64_t n, int iters, int layout, float* get_ms,
+                                float* put_ms);
+int rmx_debug_shard_row_kernels(rmx_shard* sh, int64_t id0, int64_t n, int iters, int layout, float* get_ms,
+                                float* put_ms);
 
 /* ---- samples: native LIBSVM / LIBFFM parser (host, multi-threaded) ----
  * Replaces SampleParser.parse (yr/data/SampleParser.scala:14-85) for text in memory (one sample per

@@ -399,6 +399,64 @@ extern "C" int rmx_table_upload(rmx_table* t, const float* weights, const float*
   return st;
 }
 
+// The table as row targets of the streaming engine (param_io.hip): N = 1 under the identity, so every id is
+// held here at row id.  An upload also writes the touched rows of the line copy.
+static int table_targets(const rmx_table& t, bool with_lines, RowSpace* sp, RowTarget tg[2]) {
+  sp->ctx = t.ctx;
+  sp->io = &t.io;
+  sp->op = owner_perm_of(0, t.V);
+  sp->N = 1;
+  sp->k = t.k;
+  tg[0].emb = t.emb;
+  tg[0].w = t.w;
+  tg[0].es = t.k;
+  tg[0].dt = t.dtype;
+  if (!with_lines || !t.line) return 1;
+  tg[1].emb = t.line;
+  tg[1].line = true;
+  tg[1].rs = 32;
+  tg[1].dt = t.dtype;
+  tg[1].primary = false;
+  return 2;
+}
+
+extern "C" int rmx_table_upload_rows(rmx_table* t, int64_t id0, int64_t n, const float* weights, const float* embedding,
+                                     int layout, int64_t ld) {
+  const int st = rows_check("rmx_table_upload_rows", t, t ? t->V : 0, id0, n, layout, ld);
+  if (st || n == 0) return st;
+  RMX_HIP(hipSetDevice(t->ctx->device));
+  // the line copy follows the knob as after rmx_table_upload: built from the table as it stands (or dropped)
+  // when the knob changed, then given the rows of this range
+  const bool want = t->k == 16 && tuning_get("table_lines", 0) != 0;
+  int st2;
+  if (want != (bool)t->line && (st2 = table_refresh_lines(*t))) return st2;
+  RowSpace sp;
+  RowTarget tg[2];
+  const int ntg = table_targets(*t, true, &sp, tg);
+  return rows_upload(sp, tg, ntg, id0, n, weights, embedding, layout, ld, nullptr);
+}
+
+extern "C" int rmx_table_download_rows(const rmx_table* t, int64_t id0, int64_t n, float* weights, float* embedding,
+                                       int layout, int64_t ld) {
+  const int st = rows_check("rmx_table_download_rows", t, t ? t->V : 0, id0, n, layout, ld);
+  if (st || n == 0) return st;
+  RowSpace sp;
+  RowTarget tg[2];
+  const int ntg = table_targets(*t, false, &sp, tg);
+  return rows_download(sp, tg, ntg, id0, n, weights, embedding, layout, ld, nullptr, nullptr);
+}
+
+extern "C" int rmx_debug_table_row_kernels(rmx_table* t, int64_t id0, int64_t n, int iters, int layout, float* get_ms,
+                                           float* put_ms) {
+  const int st = rows_check("rmx_debug_table_row_kernels", t, t ? t->V : 0, id0, n, layout, n);
+  if (st) return st;
+  CHECK_ARG(n > 0 && iters > 0, "rmx_debug_table_row_kernels: n and iters must be positive");
+  RowSpace sp;
+  RowTarget tg[2];
+  const int ntg = table_targets(*t, true, &sp, tg);
+  return rows_kernel_ms(sp, tg, ntg, id0, n, iters, layout == RMX_LAYOUT_K_MAJOR, get_ms, put_ms);
+}
+
 extern "C" int rmx_table_fill_synthetic(rmx_table* t, uint64_t seed) {
   CHECK_ARG(t, "rmx_table_fill_synthetic: NULL table");
   RMX_HIP(hipSetDevice(t->ctx->device));

@@ -787,4 +787,121 @@ int optim_apply(rmx_optim& o, hipStream_t s, int32_t B, const int32_t* ids, cons
   return optim_dense_update(o, s, g_bias, g_mats, loss_dev, loss, sync);
 }
 
+namespace {
+
+// the checks of the state row calls, all before any device call: the shared range checks, then the slot and the
+// parts this optimiser holds state for
+int state_rows_check(const char* who, const rmx_optim* o, int slot, int64_t id0, int64_t n, const float* weights,
+                     const float* embedding, int layout, int64_t ld) {
+  const int64_t V = !o ? 0 : o->sh ? shard_num_rows(o->sh) : o->rows;
+  int st = rows_check(who, o, V, id0, n, layout, ld);
+  if (st) return st;
+  if (slot < 0 || slot >= o->nslots) {
+    set_error(std::string(who) + ": slot " + std::to_string(slot) + ": this optimiser kind has " +
+              std::to_string(o->nslots) + " state slot(s)");
+    return RMX_E_INVALID;
+  }
+  if (weights && !o->w_s[slot]) {
+    set_error(std::string(who) + ": weights: the optimiser holds no first-order state (DNN)");
+    return RMX_E_INVALID;
+  }
+  if (embedding && !o->e_s[slot]) {
+    set_error(std::string(who) + ": embedding: the optimiser holds no embedding state (LR)");
+    return RMX_E_INVALID;
+  }
+  return RMX_OK;
+}
+
+int table_state_rows(rmx_optim& o, int slot, bool up, int64_t id0, int64_t n, float* weights, float* embedding,
+                     int layout, int64_t ld, uint8_t* owned, int64_t* count) {
+  std::lock_guard<std::mutex> lk(o.m->mu);
+  RowSpace sp;
+  sp.ctx = o.t->ctx;
+  sp.io = &o.t->io;
+  sp.op = owner_perm_of(0, o.rows);
+  sp.N = 1;
+  sp.k = o.k;
+  RowTarget tg;
+  tg.emb = o.e_s[slot];
+  tg.w = o.w_s[slot];
+  tg.es = o.k;
+  return up ? rows_upload(sp, &tg, 1, id0, n, weights, embedding, layout, ld, count)
+            : rows_download(sp, &tg, 1, id0, n, weights, embedding, layout, ld, owned, count);
+}
+
+int state_dense_check(const char* who, const rmx_optim* o, int slot) {
+  if (!o) {
+    set_error(std::string(who) + ": the optimiser is NULL");
+    return RMX_E_INVALID;
+  }
+  if (slot < 0 || slot >= o->nslots) {
+    set_error(std::string(who) + ": slot " + std::to_string(slot) + ": this optimiser kind has " +
+              std::to_string(o->nslots) + " state slot(s)");
+    return RMX_E_INVALID;
+  }
+  return RMX_OK;
+}
+
+}  // namespace
+
 }  // namespace rmx
+
+using namespace rmx;
+
+extern "C" int rmx_optim_state_upload_rows(rmx_optim* o, int slot, int64_t id0, int64_t n, const float* weights,
+                                           const float* embedding, int layout, int64_t ld, int64_t* stored) {
+  const char* who = "rmx_optim_state_upload_rows";
+  if (stored) *stored = 0;
+  const int st = state_rows_check(who, o, slot, id0, n, weights, embedding, layout, ld);
+  if (st || n == 0) return st;
+  float* w = const_cast<float*>(weights);
+  float* e = const_cast<float*>(embedding);
+  return o->sh ? shard_state_rows(who, *o, slot, true, id0, n, w, e, layout, ld, nullptr, stored)
+               : table_state_rows(*o, slot, true, id0, n, w, e, layout, ld, nullptr, stored);
+}
+
+extern "C" int rmx_optim_state_download_rows(rmx_optim* o, int slot, int64_t id0, int64_t n, float* weights,
+                                             float* embedding, int layout, int64_t ld, uint8_t* owned, int64_t* found) {
+  const char* who = "rmx_optim_state_download_rows";
+  if (found) *found = 0;
+  const int st = state_rows_check(who, o, slot, id0, n, weights, embedding, layout, ld);
+  if (st || n == 0) return st;
+  return o->sh ? shard_state_rows(who, *o, slot, false, id0, n, weights, embedding, layout, ld, owned, found)
+               : table_state_rows(*o, slot, false, id0, n, weights, embedding, layout, ld, owned, found);
+}
+
+extern "C" int rmx_optim_state_upload_dense(rmx_optim* o, int slot, const float* mats, const float* bias) {
+  const int st = state_dense_check("rmx_optim_state_upload_dense", o, slot);
+  if (st) return st;
+  rmx_model& m = *o->m;
+  std::lock_guard<std::mutex> lk(m.mu);
+  RMX_HIP(hipSetDevice(m.ctx->device));
+  RMX_HIP(hipDeviceSynchronize());  // earlier steps, whichever stream they ran on
+  if (mats && o->m_s[slot])
+    RMX_HIP(hipMemcpy(o->m_s[slot], mats, sizeof(float) * m.mats_len, hipMemcpyHostToDevice));
+  if (bias) RMX_HIP(hipMemcpy(o->b_s + slot, bias, sizeof(float), hipMemcpyHostToDevice));
+  return RMX_OK;
+}
+
+extern "C" int rmx_optim_state_download_dense(rmx_optim* o, int slot, float* mats, float* bias) {
+  const int st = state_dense_check("rmx_optim_state_download_dense", o, slot);
+  if (st) return st;
+  rmx_model& m = *o->m;
+  std::lock_guard<std::mutex> lk(m.mu);
+  RMX_HIP(hipSetDevice(m.ctx->device));
+  RMX_HIP(hipDeviceSynchronize());
+  if (mats && o->m_s[slot])
+    RMX_HIP(hipMemcpy(mats, o->m_s[slot], sizeof(float) * m.mats_len, hipMemcpyDeviceToHost));
+  if (bias) RMX_HIP(hipMemcpy(bias, o->b_s + slot, sizeof(float), hipMemcpyDeviceToHost));
+  return RMX_OK;
+}
+
+extern "C" int rmx_optim_set_steps(rmx_optim* o, int64_t t) {
+  if (!o || t < 0) {
+    set_error(!o ? "rmx_optim_set_steps: the optimiser is NULL" : "rmx_optim_set_steps: t is negative");
+    return RMX_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(o->m->mu);
+  o->steps = t;
+  return RMX_OK;
+}

@@ -7,12 +7,68 @@
 #include <string>
 #include <vector>
 
+#include "owner_perm.hpp"
 #include "rmx_internal.hpp"
 
 struct rmx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
 };
+
+namespace rmx {
+
+// Staging of the row upload / download calls (param_io.hip) of one table or shard: two pinned host chunks and
+// two device chunks of `cap` rows (knob "io_chunk_rows"), a copy stream beside the context's, and per buffer
+// the events "its copy is done" / "its kernel is done".  Sized by cap and k only, never by V; allocated at the
+// first call, reused by later ones, freed with the owner.
+struct RowIo {
+  std::mutex mu;                 // one streaming call at a time
+  int64_t cap = 0;
+  int k = 0;
+  DevBuf<float> d_emb[2];        // [cap][k] (ROW_MAJOR) or [k][rows of the chunk] (K_MAJOR)
+  DevBuf<float> d_w[2];          // [cap]
+  DevBuf<uint8_t> d_own[2];      // [cap] 1: the row's owner partition is held here
+  DevBuf<unsigned long long> d_cnt;  // [1] rows an upload stored
+  float* h_emb[2] = {nullptr, nullptr};  // pinned mirrors
+  float* h_w[2] = {nullptr, nullptr};
+  uint8_t* h_own[2] = {nullptr, nullptr};
+  unsigned long long* h_cnt = nullptr;
+  hipStream_t copy = nullptr;
+  hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_kern[2] = {nullptr, nullptr};
+  void release();                // after the owner's device synchronise
+  ~RowIo() { release(); }
+};
+
+// Where the rows of one partition (or of the whole replicated table: N = 1, part 0) live on the device.
+struct RowTarget {
+  void* emb = nullptr;   // dense: row r at emb + r * es elements (null: no such part); line: row r at emb + r * rs
+  void* w = nullptr;     // dense: w + r (null: no such part); line rows keep w at column k
+  int64_t es = 0;
+  int dt = kF32;         // element type (kF32 / kBF16)
+  bool line = false;     // [emb k | w | pad] line rows of stride rs (a shard partition, a table's line copy)
+  int rs = 0;
+  int part = 0;          // the partition held: rows with p(id) mod N == part, at local row p(id) div N
+  bool primary = true;   // counts towards stored / owned (false: a second copy of the same rows)
+};
+struct RowSpace {
+  rmx_ctx* ctx = nullptr;
+  RowIo* io = nullptr;
+  OwnerPerm op;
+  int N = 1;
+  int k = 0;
+};
+// The argument checks shared by every row call (all before any device call): handle, n, layout, ld, range.
+int rows_check(const char* who, const void* handle, int64_t V, int64_t id0, int64_t n, int layout, int64_t ld);
+// Stream host rows [id0, id0 + n) into / out of the targets, chunk by chunk; synchronous on return.
+int rows_upload(const RowSpace& sp, const RowTarget* tg, int ntg, int64_t id0, int64_t n, const float* weights,
+                const float* embedding, int layout, int64_t ld, int64_t* stored);
+int rows_download(const RowSpace& sp, const RowTarget* tg, int ntg, int64_t id0, int64_t n, float* weights,
+                  float* embedding, int layout, int64_t ld, uint8_t* owned, int64_t* found);
+// ms per launch of the get and of the put kernel alone over rows [id0, id0 + n) held in a device chunk
+int rows_kernel_ms(const RowSpace& sp, const RowTarget* tg, int ntg, int64_t id0, int64_t n, int iters, int kmajor,
+                   float* get_ms, float* put_ms);
+
+}  // namespace rmx
 
 struct rmx_table {
   rmx_ctx* ctx = nullptr;
@@ -29,6 +85,7 @@ struct rmx_table {
   // (rmx::model_reads_lines).  Measured ~1 % SLOWER for DeepFM layer 1 at V = 1M (0.1851 vs 0.1829 ms,
   // two A/B pairs on one box): the weight lines it saves hit the Infinity Cache, so it is off.
   rmx::DevBuf<float> line;  // (bf16 tables: bf16 elements, half as many floats)
+  mutable rmx::RowIo io;    // staging of rmx_table_upload_rows / _download_rows and of its optimiser's state calls
 };
 
 namespace rmx {
@@ -346,6 +403,11 @@ struct StageTimer {
 int shard_create(rmx_ctx* ctx, int64_t V, int k, int N, int rank, const void* unique_id, rmx_group* group,
                  rmx_shard** out);
 int shard_destroy(rmx_shard* sh);
+// The state row calls of a sharded optimiser (shard.hip; takes the shard's lock, then the model's): slot's
+// [rows][k] / [rows] blocks of the partitions held here as dense targets.  up: upload (else download).
+int shard_state_rows(const char* who, rmx_optim& o, int slot, bool up, int64_t id0, int64_t n, float* weights,
+                     float* embedding, int layout, int64_t ld, uint8_t* owned, int64_t* count);
+int64_t shard_num_rows(const rmx_shard* sh);
 
 // kernels specific to the interaction encoders
 int launch_pack_cin(hipStream_t s, const float* mats, int F, CinLayer& L);

@@ -102,6 +102,8 @@ struct rmx_shard {
   int64_t rows_per = 0;                 // ceil(V / N) local rows per partition
   uint64_t owner_key = RMX_OWNER_HASH_DEFAULT;  // Feistel key of p (set_owner_hash); 0: owner = id mod N
   bool filled = false;                  // rows written (the owner function is then fixed)
+  bool cleared = false;                 // an unfilled shard's partitions were zeroed by a row call
+  rmx::RowIo io;                        // staging of rmx_shard_upload_rows / _download_rows and of its optimiser's state calls
   int rs = 0;                           // row stride in floats: [emb k | w | pad], one 128-B line at k < 32
   std::vector<rmx::DevBuf<float>> part;  // partitions held here: [rows_per + 1][rs] (loopback: N); the
                                         // extra row stays zero (the row of an out-of-range id read in place)
@@ -222,73 +224,8 @@ __device__ __forceinline__ int wave_reserve(int o, int* h) {
 // Routing = count -> scan -> scatter with no global atomics: block b histograms its tile of
 // kRouteTile ids by owner into bcnt[o][b] (wave-aggregated LDS counters), one block per owner scans
 // its column into the tile's start offset, and the scatter pass recomputes the in-tile ranks.
-// The keyed permutation p of [0, V) (OwnerPerm.key == 0: identity): a 4-round Feistel network on
-// the square domain Z_a x Z_a, a = ceil(sqrt(V)) (x = L a + R), each round (L, R) -> (R, (L + F_r(R))
-// mod a) with F_r(R) = mulhi(fmix32(R ^ k_r), a) (the murmur3 finaliser; k_r four 32-bit round keys
-// drawn from the key by splitmix64).  Cycle-walked back into [0, V): the domain exceeds V by < 2a,
-// so a walk is rare (none at V = a^2, e.g. V = 10^8); every cycle re-enters [0, V) only if it started
-// there.  All 32-bit integer work, ~40 instructions per id.
-struct OwnerPerm {
-  uint64_t key = 0;
-  uint32_t a = 1;
-  uint32_t rk[4] = {0, 0, 0, 0};
-  int64_t V = 0;
-};
-__device__ __host__ __forceinline__ uint32_t owner_round(uint32_t x, uint32_t rk, uint32_t a) {
-  uint32_t h = x ^ rk;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return (uint32_t)(((uint64_t)h * a) >> 32);  // uniform in [0, a)
-}
-__device__ __host__ __forceinline__ uint32_t feistel_once(uint32_t x, const OwnerPerm& op, bool inverse) {
-  const uint32_t a = op.a;
-  uint32_t L = x / a, R = x - L * a;
-  if (!inverse) {
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t t = owner_round(R, op.rk[r], a);
-      const uint32_t s = L + t;
-      L = R;
-      R = s >= a ? s - a : s;
-    }
-  } else {
-    for (int r = 3; r >= 0; --r) {
-      const uint32_t t = owner_round(L, op.rk[r], a);
-      const uint32_t l = R >= t ? R - t : R + a - t;
-      R = L;
-      L = l;
-    }
-  }
-  return L * a + R;
-}
-__device__ __host__ __forceinline__ int64_t owner_perm(int64_t id, const OwnerPerm& op, bool inverse) {
-  if (!op.key) return id;
-  uint32_t y = feistel_once((uint32_t)id, op, inverse);
-  while ((int64_t)y >= op.V) y = feistel_once(y, op, inverse);
-  return y;
-}
-
-OwnerPerm owner_perm_of(uint64_t key, int64_t V) {
-  OwnerPerm op;
-  op.key = key;
-  op.V = V;
-  uint64_t a = (uint64_t)std::sqrt((double)std::max<int64_t>(V, 1));
-  while ((int64_t)(a * a) < V) ++a;
-  while (a > 1 && (int64_t)((a - 1) * (a - 1)) >= V) --a;
-  op.a = (uint32_t)a;
-  uint64_t z = key;
-  for (int r = 0; r < 4; ++r) {  // round keys: splitmix64 of the key, successive states
-    z += 0x9E3779B97F4A7C15ULL;
-    uint64_t x = z;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    op.rk[r] = (uint32_t)(x ^ (x >> 31));
-  }
-  return op;
-}
-OwnerPerm owner_perm_of(const rmx_shard& sh) { return owner_perm_of(sh.owner_key, sh.V); }
+// (The keyed permutation p of [0, V) itself: owner_perm.hpp.)
+OwnerPerm owner_perm_of(const rmx_shard& sh) { return rmx::owner_perm_of(sh.owner_key, sh.V); }
 
 __device__ __forceinline__ int route_owner(const int32_t* ids, int64_t n, int64_t nnz, int N, int* loc,
                                            const OwnerPerm& op) {
@@ -1929,6 +1866,126 @@ extern "C" int rmx_shard_fill_synthetic(rmx_shard* sh, uint64_t seed) {
     return RMX_E_INVALID;
   }
   return shard_fill_synthetic(*sh, seed);
+}
+
+namespace rmx {
+namespace {
+
+// The row calls read and write the partitions in place: refused while a pull slot holds an unconsumed pull (a
+// direct slot's forward reads the partition itself).  The shard's lock is held by the caller.
+int shard_rows_ready(const char* who, rmx_shard& sh) {
+  for (int q = 0; q < 2; ++q)
+    if (sh.slot_nnz[q] >= 0) {
+      set_error(std::string(who) + ": pull slot " + std::to_string(q) + " holds a pull that has not been consumed");
+      return RMX_E_INVALID;
+    }
+  if (sh.failed) {
+    set_error(std::string(who) + ": the shard has failed (rmx_shard_abort, then a new shard)");
+    return RMX_E_COMM;
+  }
+  return RMX_OK;
+}
+
+void shard_row_space(rmx_shard& sh, RowSpace* sp) {
+  sp->ctx = sh.ctx;
+  sp->io = &sh.io;
+  sp->op = owner_perm_of(sh);
+  sp->N = sh.N;
+  sp->k = sh.k;
+}
+
+// a shard nothing has written yet holds whatever the allocation held: rows never uploaded must read as zeros
+int shard_clear_unfilled(rmx_shard& sh) {
+  if (sh.filled || sh.cleared) return RMX_OK;
+  RMX_HIP(hipSetDevice(sh.ctx->device));
+  for (float* q : sh.part)
+    RMX_HIP(hipMemsetAsync(q, 0, sizeof(float) * (size_t)(sh.rows_per + 1) * sh.rs, sh.ctx->stream));
+  RMX_HIP(hipStreamSynchronize(sh.ctx->stream));
+  sh.cleared = true;
+  return RMX_OK;
+}
+
+}  // namespace
+
+int64_t shard_num_rows(const rmx_shard* sh) { return sh ? sh->V : 0; }
+
+int shard_state_rows(const char* who, rmx_optim& o, int slot, bool up, int64_t id0, int64_t n, float* weights,
+                     float* embedding, int layout, int64_t ld, uint8_t* owned, int64_t* count) {
+  rmx_shard& sh = *o.sh;
+  std::lock_guard<std::mutex> lk(sh.mu);
+  int st = shard_rows_ready(who, sh);
+  if (st) return st;
+  std::lock_guard<std::mutex> lm(o.m->mu);
+  RowSpace sp;
+  shard_row_space(sh, &sp);
+  std::vector<RowTarget> tg(o.nparts);
+  for (int p = 0; p < o.nparts; ++p) {
+    tg[p].emb = o.e_s[slot] ? o.e_s[slot] + (size_t)p * o.rows * o.k : nullptr;
+    tg[p].w = o.w_s[slot] ? o.w_s[slot] + (size_t)p * o.rows : nullptr;
+    tg[p].es = o.k;
+    tg[p].part = sh.loopback ? p : sh.rank;
+  }
+  return up ? rows_upload(sp, tg.data(), o.nparts, id0, n, weights, embedding, layout, ld, count)
+            : rows_download(sp, tg.data(), o.nparts, id0, n, weights, embedding, layout, ld, owned, count);
+}
+
+}  // namespace rmx
+
+static void shard_targets(const rmx_shard& sh, std::vector<RowTarget>* tg) {
+  tg->resize(sh.part.size());
+  for (size_t p = 0; p < sh.part.size(); ++p) {
+    (*tg)[p].emb = sh.part[p];
+    (*tg)[p].line = true;
+    (*tg)[p].rs = sh.rs;
+    (*tg)[p].part = sh.loopback ? (int)p : sh.rank;
+  }
+}
+
+extern "C" int rmx_shard_upload_rows(rmx_shard* sh, int64_t id0, int64_t n, const float* weights, const float* embedding,
+                                     int layout, int64_t ld, int64_t* stored) {
+  int st = rows_check("rmx_shard_upload_rows", sh, sh ? sh->V : 0, id0, n, layout, ld);
+  if (stored) *stored = 0;
+  if (st || n == 0) return st;
+  std::lock_guard<std::mutex> lk(sh->mu);
+  if ((st = shard_rows_ready("rmx_shard_upload_rows", *sh)) || (st = shard_clear_unfilled(*sh))) return st;
+  RowSpace sp;
+  shard_row_space(*sh, &sp);
+  std::vector<RowTarget> tg;
+  shard_targets(*sh, &tg);
+  st = rows_upload(sp, tg.data(), (int)tg.size(), id0, n, weights, embedding, layout, ld, stored);
+  if (st == RMX_OK) sh->filled = true;  // rows are placed: the owner function is fixed from here on
+  return st;
+}
+
+extern "C" int rmx_shard_download_rows(rmx_shard* sh, int64_t id0, int64_t n, float* weights, float* embedding,
+                                       int layout, int64_t ld, uint8_t* owned, int64_t* found) {
+  int st = rows_check("rmx_shard_download_rows", sh, sh ? sh->V : 0, id0, n, layout, ld);
+  if (found) *found = 0;
+  if (st || n == 0) return st;
+  std::lock_guard<std::mutex> lk(sh->mu);
+  if ((st = shard_rows_ready("rmx_shard_download_rows", *sh)) || (st = shard_clear_unfilled(*sh))) return st;
+  RowSpace sp;
+  shard_row_space(*sh, &sp);
+  std::vector<RowTarget> tg;
+  shard_targets(*sh, &tg);
+  return rows_download(sp, tg.data(), (int)tg.size(), id0, n, weights, embedding, layout, ld, owned, found);
+}
+
+extern "C" int rmx_debug_shard_row_kernels(rmx_shard* sh, int64_t id0, int64_t n, int iters, int layout, float* get_ms,
+                                           float* put_ms) {
+  int st = rows_check("rmx_debug_shard_row_kernels", sh, sh ? sh->V : 0, id0, n, layout, n);
+  if (st) return st;
+  if (n <= 0 || iters <= 0) {
+    set_error("rmx_debug_shard_row_kernels: n and iters must be positive");
+    return RMX_E_INVALID;
+  }
+  std::lock_guard<std::mutex> lk(sh->mu);
+  if ((st = shard_rows_ready("rmx_debug_shard_row_kernels", *sh)) || (st = shard_clear_unfilled(*sh))) return st;
+  RowSpace sp;
+  shard_row_space(*sh, &sp);
+  std::vector<RowTarget> tg;
+  shard_targets(*sh, &tg);
+  return rows_kernel_ms(sp, tg.data(), (int)tg.size(), id0, n, iters, layout == RMX_LAYOUT_K_MAJOR, get_ms, put_ms);
 }
 
 extern "C" int64_t rmx_shard_local_rows(const rmx_shard* sh) { return sh ? sh->rows_per : -1; }

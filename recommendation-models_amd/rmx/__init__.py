@@ -219,6 +219,64 @@ class DeviceArray:
             pass
 
 
+def _vp(a):
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def _kmajor_view(e, k):
+    """A [k][n] fp32 array whose rows are contiguous (e.g. columns [a, b) of a [k][V] matrix): usable in place
+    with ld = its row pitch."""
+    return (isinstance(e, np.ndarray) and e.ndim == 2 and e.dtype == np.float32 and e.shape[0] == k
+            and e.strides[1] == 4 and e.strides[0] % 4 == 0 and e.strides[0] >= 4 * e.shape[1])
+
+
+def _host_range(k, weights, embedding, layout, ld):
+    """The host arrays of an upload as (weights, embedding, n, ld): fp32, contiguous in the given layout."""
+    w = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1)
+    e = None
+    n = None if w is None else w.size  # rows of the range: the weights', else the embedding's
+    if embedding is not None and k > 0:
+        if layout == LAYOUT_K_MAJOR and ld is None and _kmajor_view(embedding, k):
+            e, ld, ne = embedding, embedding.strides[0] // 4, embedding.shape[1]
+        elif layout == LAYOUT_K_MAJOR:
+            e = np.ascontiguousarray(embedding, np.float32)
+            ld = e.size // k if ld is None else int(ld)
+            if e.size != k * ld:
+                raise ValueError("a K_MAJOR embedding must have k * ld entries")
+            ne = ld if n is None else min(n, ld)  # (ld > n: the range is the first n columns)
+        else:
+            e = np.ascontiguousarray(embedding, np.float32)
+            ne = e.size // k
+            if e.size != ne * k:
+                raise ValueError("embedding must have n * k entries")
+        if n is not None and ne != n:
+            raise ValueError("weights and embedding cover different numbers of rows")
+        n = ne
+    n = 0 if n is None else int(n)
+    return w, e, n, int(ld if ld is not None else n)
+
+
+def _host_out(k, n, layout, weights=None, embedding=None):
+    """The host arrays of a download as (weights, embedding, ld): the caller's (fp32, [n] and [n][k] contiguous or
+    [k][n] with contiguous rows) or new ones."""
+    if weights is None:
+        weights = np.zeros(n, np.float32)
+    elif not (weights.dtype == np.float32 and weights.flags.c_contiguous and weights.size == n):
+        raise ValueError("download: weights must be a contiguous float32 array of n entries")
+    ld = n
+    if k <= 0:
+        return weights, None, ld
+    if embedding is None:
+        embedding = np.zeros((k, n) if layout == LAYOUT_K_MAJOR else (n, k), np.float32)
+    elif layout == LAYOUT_K_MAJOR:
+        if not (_kmajor_view(embedding, k) and embedding.shape[1] == n):
+            raise ValueError("download: a K_MAJOR embedding must be float32 [k][n] with contiguous rows")
+        ld = embedding.strides[0] // 4
+    elif not (embedding.dtype == np.float32 and embedding.flags.c_contiguous and embedding.size == n * k):
+        raise ValueError("download: embedding must be a contiguous float32 array of n * k entries")
+    return weights, embedding, int(ld)
+
+
 class EmbeddingTable:
     """HBM-resident first-order weights [V] + embeddings [V][k]: replaces the Angel PS matrices
     "weights" and "embedding" (ParRecModel.scala:74-105) and their pull + make* gather
@@ -249,6 +307,24 @@ class EmbeddingTable:
 
     def fill_synthetic(self, seed):
         check(_lib.lib.rmx_table_fill_synthetic(self.handle, int(seed)))
+
+    def upload_rows(self, id0, weights=None, embedding=None, layout=LAYOUT_ROW_MAJOR, ld=None):
+        """Rows [id0, id0 + n) from host arrays (rmx_table_upload_rows): weights [n], embedding [n][k]
+        (LAYOUT_ROW_MAJOR) or [k][ld] with ld >= n (LAYOUT_K_MAJOR; ld defaults to the array's row length).
+        Either may be None (left as it is).  Streams through bounded staging (knob io_chunk_rows)."""
+        w, e, n, ld = _host_range(self.k, weights, embedding, layout, ld)
+        check(_lib.lib.rmx_table_upload_rows(self.handle, int(id0), n, _vp(w), _vp(e), int(layout), ld))
+
+    def download_rows(self, id0, n, layout=LAYOUT_ROW_MAJOR, weights=None, embedding=None):
+        """(weights [n], embedding [n][k] or [k][n]) of rows [id0, id0 + n) as fp32 (rmx_table_download_rows);
+        weights / embedding: arrays to fill instead of new ones (e.g. slices of a memmap)."""
+        w, e, ld = _host_out(self.k, int(n), layout, weights, embedding)
+        check(_lib.lib.rmx_table_download_rows(self.handle, int(id0), int(n), _vp(w), _vp(e), int(layout), ld))
+        return w, e
+
+    def download(self, layout=LAYOUT_ROW_MAJOR):
+        """The whole table: (weights [V], embedding [V][k] or [k][V])."""
+        return self.download_rows(0, self.rows, layout)
 
     def refresh_lines(self):
         """Rebuild (or, with knob table_lines 0, drop) the [rows][32] line copy of an fp32 k = 16 table."""
@@ -331,10 +407,30 @@ class ShardedTable:
         self.k = int(embedding_dim)
         self.nranks = int(nranks)
         self.rank = int(rank)
+        self.loopback = group is None and unique_id is None  # every partition lives in this object
         _track("shard", self)
 
     def fill_synthetic(self, seed):
         check(_lib.lib.rmx_shard_fill_synthetic(self.handle, int(seed)))
+
+    def upload_rows(self, id0, weights=None, embedding=None, layout=LAYOUT_ROW_MAJOR, ld=None):
+        """Rows [id0, id0 + n) from host arrays (EmbeddingTable.upload_rows' arguments); a LOCAL call: the rows
+        whose owner partition lives in this object are kept, the others skipped (rmx_shard_upload_rows).  Returns
+        the number of rows kept."""
+        w, e, n, ld = _host_range(self.k, weights, embedding, layout, ld)
+        stored = ctypes.c_int64(0)
+        check(_lib.lib.rmx_shard_upload_rows(self.handle, int(id0), n, _vp(w), _vp(e), int(layout), ld,
+                                             ctypes.byref(stored)))
+        return int(stored.value)
+
+    def download_rows(self, id0, n, layout=LAYOUT_ROW_MAJOR, weights=None, embedding=None):
+        """(weights, embedding, owned) of rows [id0, id0 + n): owned [n] bool marks the rows held here; the
+        elements of the others are not written (zeros in new arrays; rmx_shard_download_rows).  Local call."""
+        w, e, ld = _host_out(self.k, int(n), layout, weights, embedding)
+        owned = np.zeros(int(n), np.uint8)
+        check(_lib.lib.rmx_shard_download_rows(self.handle, int(id0), int(n), _vp(w), _vp(e), int(layout), ld,
+                                               _vp(owned), None))
+        return w, e, owned.astype(bool)
 
     def local_rows(self):
         return int(_lib.lib.rmx_shard_local_rows(self.handle))
@@ -448,6 +544,17 @@ def debug_poison_workspace(model, pattern=0x7FC07FC0, stream=None):
     h = model._dev if model._dev is not None else model._meta
     check(_lib.lib.rmx_debug_poison_workspace(h, int(pattern) & 0xFFFFFFFF, stream, ctypes.byref(n)))
     return int(n.value)
+
+
+def debug_row_kernels(obj, id0, n, iters=20, layout=LAYOUT_ROW_MAJOR):
+    """Test / bench hook: (get_ms, put_ms) per launch of the row gather and scatter kernels alone over rows
+    [id0, id0 + n) of an EmbeddingTable or ShardedTable held in a device chunk (n at most io_chunk_rows); the rows
+    are unchanged (rmx_debug_table_row_kernels / rmx_debug_shard_row_kernels)."""
+    fn = (_lib.lib.rmx_debug_shard_row_kernels if isinstance(obj, ShardedTable)
+          else _lib.lib.rmx_debug_table_row_kernels)
+    g, p = ctypes.c_float(), ctypes.c_float()
+    check(fn(obj.handle, int(id0), int(n), int(iters), int(layout), ctypes.byref(g), ctypes.byref(p)))
+    return g.value, p.value
 
 
 def debug_live_device_memory():
@@ -796,6 +903,7 @@ class Optimizer:
         self.table = None if sharded else table
         self.shard = table if sharded else None
         self.kind = int(kind)
+        self.hyper = {n: float(hyper.get(n, d)) for n, d in names}  # with the defaults filled in (checkpoint meta)
         _track("optim", self)
 
     def shard_state_ptrs(self, slot, part=0):
@@ -810,6 +918,55 @@ class Optimizer:
     @property
     def steps(self):
         return int(_lib.lib.rmx_optim_steps(self.handle)) if self.handle else 0
+
+    @steps.setter
+    def steps(self, t):
+        """The step count (rmx_optim_set_steps): the next apply uses t + 1."""
+        check(_lib.lib.rmx_optim_set_steps(self.handle, int(t)))
+
+    @property
+    def nslots(self):
+        """State slots per parameter: SGD 0, Momentum / Adagrad 1, Adam 2."""
+        return {_lib.OPTIM_SGD: 0, _lib.OPTIM_ADAM: 2}.get(self.kind, 1)
+
+    def state_upload_rows(self, slot, id0, weights=None, embedding=None, layout=LAYOUT_ROW_MAJOR, ld=None):
+        """State slot `slot` of rows [id0, id0 + n) from host arrays (rmx_optim_state_upload_rows; arguments and
+        ownership as the table's or shard's upload_rows).  Returns the number of rows kept."""
+        k = (self.table or self.shard).k
+        w, e, n, ld = _host_range(k, weights, embedding, layout, ld)
+        stored = ctypes.c_int64(0)
+        check(_lib.lib.rmx_optim_state_upload_rows(self.handle, int(slot), int(id0), n, _vp(w), _vp(e), int(layout),
+                                                   ld, ctypes.byref(stored)))
+        return int(stored.value)
+
+    def state_download_rows(self, slot, id0, n, layout=LAYOUT_ROW_MAJOR, want_weights=True, want_embedding=True):
+        """(weights, embedding, owned) of state slot `slot` of rows [id0, id0 + n); a part the optimiser holds no
+        state for (LR's embedding, DNN's first order) must not be asked for (rmx_optim_state_download_rows)."""
+        k = (self.table or self.shard).k
+        n = int(n)
+        w = np.zeros(n, np.float32) if want_weights else None
+        e = (np.zeros((k, n) if layout == LAYOUT_K_MAJOR else (n, k), np.float32)
+             if want_embedding and k > 0 else None)
+        ld = n
+        owned = np.zeros(int(n), np.uint8)
+        check(_lib.lib.rmx_optim_state_download_rows(self.handle, int(slot), int(id0), int(n), _vp(w), _vp(e),
+                                                     int(layout), ld, _vp(owned), None))
+        return w, e, owned.astype(bool)
+
+    def state_upload_dense(self, slot, mats=None, bias=None):
+        """State slot `slot` of mats [mats_len] and of the bias (each None: left as it is)."""
+        m = None if mats is None else np.ascontiguousarray(mats, np.float32).reshape(-1)
+        if m is not None and m.size != self.model.matsLength():
+            raise ValueError("mats state must have matsLength() entries")
+        b = None if bias is None else np.asarray(bias, np.float32).reshape(-1)[:1].copy()
+        check(_lib.lib.rmx_optim_state_upload_dense(self.handle, int(slot), _vp(m), _vp(b)))
+
+    def state_download_dense(self, slot):
+        """(mats state [mats_len], bias state) of slot `slot`."""
+        m = np.zeros(self.model.matsLength(), np.float32)
+        b = np.zeros(1, np.float32)
+        check(_lib.lib.rmx_optim_state_download_dense(self.handle, int(slot), _vp(m) if m.size else None, _vp(b)))
+        return m, float(b[0])
 
     def apply(self, batch, ids_dev, g_bias=None, g_weights=None, g_embedding=None, g_mats=None, stream=None):
         """One step from the per-nonzero gradients of backward_ids (DeviceArrays; None leaves the group

@@ -138,6 +138,18 @@ SIGNATURES = [
     ("rmx_optim_create_sharded", c_int, [c_vp, c_vp, c_int, P(ctypes.c_double), c_int, P(c_vp)]),
     ("rmx_optim_shard_state_ptrs", c_int, [c_vp, c_int, c_int, P(c_vp), P(c_vp)]),
     ("rmx_train_step_sharded", c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, P(c_f32), c_vp]),
+    ("rmx_table_upload_rows", c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_i64]),
+    ("rmx_table_download_rows", c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_i64]),
+    ("rmx_shard_upload_rows", c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, P(c_i64)]),
+    ("rmx_shard_download_rows", c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, P(c_i64)]),
+    ("rmx_optim_state_upload_rows", c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, P(c_i64)]),
+    ("rmx_optim_state_download_rows", c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_int, c_i64, c_vp,
+                                              P(c_i64)]),
+    ("rmx_optim_state_upload_dense", c_int, [c_vp, c_int, c_vp, c_vp]),
+    ("rmx_optim_state_download_dense", c_int, [c_vp, c_int, c_vp, c_vp]),
+    ("rmx_optim_set_steps", c_int, [c_vp, c_i64]),
+    ("rmx_debug_table_row_kernels", c_int, [c_vp, c_i64, c_i64, c_int, c_int, P(c_f32), P(c_f32)]),
+    ("rmx_debug_shard_row_kernels", c_int, [c_vp, c_i64, c_i64, c_int, c_int, P(c_f32), P(c_f32)]),
 ]
 
 for _name, _res, _args in SIGNATURES:
