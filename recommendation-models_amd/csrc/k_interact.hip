@@ -143,6 +143,8 @@ int launch_cross_finish(hipStream_t s, int B, int L, const float* xcol, const Cr
   return RMX_OK;
 }
 
+// (tests/shape_cases.py restates this choice of kernel -- cross16_fmax -- to name the rows that reach each
+// instantiation: keep the two in step)
 int launch_cross(hipStream_t s, int B, int F, int k, int L, const int32_t* ids, const void* table, int dt,
                  const float* cross_w, const float* cross_b, const float* wo_x, float* pre2) {
   if (B <= 0) return RMX_OK;
@@ -283,6 +285,8 @@ __global__ __launch_bounds__(256) void product16_kernel(int B, int F, const int3
   }
 }
 
+// (tests/shape_cases.py restates this choice of kernel -- product_ntile -- to name the rows that reach each
+// NTILE and the generic kernel: keep the two in step)
 int launch_product(hipStream_t s, int B, int F, int k, const int32_t* ids, const void* table, int dt,
                    const int32_t* pairs, int P, void* xbuf, int xdt, int ldx) {
   if (B <= 0) return RMX_OK;
@@ -308,20 +312,32 @@ int launch_product(hipStream_t s, int B, int F, int k, const int32_t* ids, const
     RMX_HIP(hipGetLastError());
     return RMX_OK;
   }
-  const size_t lds = sizeof(float) * 4 * (F * k + 1);
+  // four samples' rows [F k + 1] in LDS: above the 64 KB a kernel gets by default the attribute is set (at
+  // every launch, as launch_cfg does: a process may drive several devices); model_build refuses what no CU holds
+  if (!product_fits_lds(F, k)) {
+    set_error("product: nFields * embeddingDim must be <= " + std::to_string(kProductMaxD) +
+              " (the generic product kernel keeps four samples' rows in the 160 KB of LDS)");
+    return RMX_E_INVALID;
+  }
+  const size_t lds = product_lds_bytes(F, k);
   const dim3 grid((B + 3) / 4), blk(256);
+#define RMX_PRODG(T, X)                                                                                            \
+  {                                                                                                                \
+    if (lds > 64 * 1024)                                                                                           \
+      RMX_HIP(hipFuncSetAttribute((const void*)product_kernel<T, X>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                  (int)lds));                                                                      \
+    hipLaunchKernelGGL((product_kernel<T, X>), grid, blk, lds, s, B, F, k, ids, (const T*)table, pairs, P,         \
+                       (X*)xbuf, ldx);                                                                             \
+  }
   if (dt == kBF16 && xdt == kBF16)
-    hipLaunchKernelGGL((product_kernel<bf16_t, bf16_t>), grid, blk, lds, s, B, F, k, ids, (const bf16_t*)table, pairs,
-                       P, (bf16_t*)xbuf, ldx);
+    RMX_PRODG(bf16_t, bf16_t)
   else if (dt == kBF16)
-    hipLaunchKernelGGL((product_kernel<bf16_t, float>), grid, blk, lds, s, B, F, k, ids, (const bf16_t*)table, pairs,
-                       P, (float*)xbuf, ldx);
+    RMX_PRODG(bf16_t, float)
   else if (xdt == kBF16)
-    hipLaunchKernelGGL((product_kernel<float, bf16_t>), grid, blk, lds, s, B, F, k, ids, (const float*)table, pairs,
-                       P, (bf16_t*)xbuf, ldx);
+    RMX_PRODG(float, bf16_t)
   else
-    hipLaunchKernelGGL((product_kernel<float, float>), grid, blk, lds, s, B, F, k, ids, (const float*)table, pairs, P,
-                       (float*)xbuf, ldx);
+    RMX_PRODG(float, float)
+#undef RMX_PRODG
   RMX_HIP(hipGetLastError());
   return RMX_OK;
 }

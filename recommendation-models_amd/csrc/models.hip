@@ -195,6 +195,10 @@ int model_build(rmx_model& m) {
     set_error("PNN needs at least two fields");
     return RMX_E_INVALID;
   }
+  if (t == RMX_MODEL_PNN && !product_fits_lds(m.F, m.k)) {
+    set_error("PNN product kernel supports nFields*embeddingDim <= " + std::to_string(kProductMaxD));
+    return RMX_E_INVALID;
+  }
   m.sizes = mats_sizes(m);
   m.mats_len = 0;
   for (size_t i = 0; i < m.sizes.size(); i += 2) m.mats_len += (int64_t)m.sizes[i] * m.sizes[i + 1];

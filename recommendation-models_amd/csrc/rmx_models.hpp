@@ -423,6 +423,11 @@ int launch_cross(hipStream_t s, int B, int F, int k, int L, const int32_t* ids, 
                  const float* cross_w, const float* cross_b, const float* wo_x, float* pre2);
 int launch_product(hipStream_t s, int B, int F, int k, const int32_t* ids, const void* table, int dt,
                    const int32_t* pairs, int P, void* xbuf, int xdt, int ldx);
+// the generic product kernel's dynamic LDS: the rows [F k + 1] of a block's four samples, at most a CU's 160 KB
+// (every PNN can reach it: the host-array forward passes no id array, which the k = 16 kernel needs)
+constexpr int kProductMaxD = 160 * 1024 / 16 - 1;
+inline size_t product_lds_bytes(int F, int k) { return sizeof(float) * 4 * ((size_t)F * k + 1); }
+inline bool product_fits_lds(int F, int k) { return (int64_t)F * k <= kProductMaxD; }
 int launch_gather_x(hipStream_t s, int B, int F, int k, const int32_t* ids, const void* table, int dt, void* xbuf,
                     int xdt, int ldx);
 int tower_npad_for(int N);

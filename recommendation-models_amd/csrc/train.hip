@@ -288,6 +288,19 @@ __global__ void relu_back_kernel(int B, int N, const float* __restrict__ h, int 
   if (!(h[b * ldh + n] > 0.f)) g[b * ldg + n] = 0.f;
 }
 
+// The split GEMM (dX: launch_dx_s3, the CIN's dL/dz: launch_cin_dz_s3) stages its dense A operand in 16-byte
+// slots, so with K % 4 != 0 the last slot of a row also carries columns [K, round_up(K, 4)) of g.  The kernels
+// that produce dPre / gpre write columns < K only; the rest is whatever the scratch held.  It meets zero weight
+// planes, so a finite leftover is harmless and a NaN / Inf one (0 * NaN) turns the whole output row into NaN:
+// zero those columns first.
+__global__ void zero_k_tail_kernel(int64_t rows, int K, float* __restrict__ g, int ldg) {
+  const int pad = (4 - (K & 3)) & 3;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * pad) return;
+  const int64_t r = i / pad;
+  g[r * ldg + K + (int)(i - r * pad)] = 0.f;
+}
+
 // dL/dE[b][f][j] = dx[b][f*k + j] (+ FM: dz[b] * (s_j - e[b][f][j]) / k), thread per (b, j)
 __global__ void emb_grad_kernel(int B, int F, int k, const float* __restrict__ x, int ldx,
                                 const float* __restrict__ dx, int lddx, const float* __restrict__ dz, int fm,
@@ -1342,6 +1355,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(int rows, int N, const floa
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+int zero_k_tail(hipStream_t s, int64_t rows, int K, float* g, int ldg) {
+  if (K % 4 == 0 || rows <= 0) return RMX_OK;
+  hipLaunchKernelGGL(zero_k_tail_kernel, dim3(nblk(rows * (4 - K % 4))), dim3(256), 0, s, rows, K, g, ldg);
+  RMX_HIP(hipGetLastError());
+  return RMX_OK;
+}
+
 int ensure_part(TrainState& T, int64_t n) {
   if (n <= T.cap_part) return RMX_OK;
   RMX_HIP(hipDeviceSynchronize());
@@ -1912,6 +1932,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
       bias_done = bias_done || bd;
       if (!need_dx) continue;
       if (nb == 1 && m.precision == kF32 && dx_s3_usable(L, ldin) && (!mask || L.NTpad <= ldmask)) {
+        if ((st = zero_k_tail(s, B, L.N, T.g[cur], L.Npad))) return st;  // (dpre; the split GEMM's K is L.N)
         // DeepFM layer 1: dX + the FM term written straight as the embedding gradient (emb_grad_kernel's
         // arithmetic in the dX epilogue: dX is never stored and reread)
         emb_fused = l == 0 && t == RMX_MODEL_DEEPFM && T.fms_valid && o.g_emb && ldin == D && L.K == D;
@@ -1991,6 +2012,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
       hipLaunchKernelGGL(cin_gpre_kernel, dim3(nblk(R * H)), dim3(256), 0, s, R, H, k, T.u[l], ldu,
                          l == nc - 1 ? nullptr : T.gu[gcur], T.dz, c.wo, T.gpre);
       RMX_HIP(hipGetLastError());
+      if ((st = zero_k_tail(s, R, H, T.gpre, ldu))) return st;  // launch_cin_dz_s3 below reads gpre with K = H
       if (o.g_mats) {
         // pooled slice of W_out: sum_r dz[b] u_l[r][h]; bias c_l: sum_r gpre[r][h]
         if ((st = colsum(T, s, (int)R, H, T.u[l], ldu, T.dzr, o.g_mats + c.wo_off, false))) return st;
