@@ -38,6 +38,15 @@ def hyper(kind, **kw):
     return hp
 
 
+def radix_passes(V):
+    """(bits, passes) of the device's id sort on a table of V rows (optim.hip id_bits, restated): the bits of the
+    largest key -- V itself, the key given to an id outside the table -- and one 8-bit pass per started byte."""
+    bits = 1
+    while V >> bits:
+        bits += 1
+    return bits, (bits + 7) // 8
+
+
 def _seq_sum32(rows, starts, counts):
     """Per list i: the sequential fp32 sum of rows[starts[i] : starts[i] + counts[i]] starting from the first
     term.  rows [n, c] float32; vectorised over the lists, sequential along each."""

@@ -1,6 +1,7 @@
 """Device-resident optimiser step (rmx_optim_*, rmx_train_step_ids) on the GPU against tests/optim_ref.py.
 
-V = 2,000 everywhere, so a batch holds many duplicate ids.  The apply tests upload synthetic random gradients:
+V = 2,000 unless a test names its own (the radix-pass tables, the sweep's rows), so a batch holds many duplicate
+ids.  The apply tests upload synthetic random gradients:
 nothing there depends on the backward.
 
 Bars.  Bitwise: SGD at eta = 1.0 (eta g is exact and p - g takes one rounding with or without an FMA), so the
@@ -32,7 +33,7 @@ def same_bits(a, b):
     return np.array_equal(bits(a), bits(b))
 
 
-def make_model(kind, F, k, fc=FC):
+def make_model(kind, F, k, fc=FC, V=V):
     return {"lr": lambda: rmx.LR(V, F), "deepfm": lambda: rmx.DeepFM(V, F, k, list(fc)),
             "dnn": lambda: rmx.DNN(V, F, k, list(fc)), "dcn": lambda: rmx.DCN(V, F, k, 3, list(fc)),
             "pnn": lambda: rmx.PNN(V, F, k, list(fc)),
@@ -42,28 +43,32 @@ def make_model(kind, F, k, fc=FC):
 _TABLES = {}
 
 
-def table_values(k):
-    """The initial table of every test (computed once per k, never changed)."""
-    if k not in _TABLES:
+def table_values(k, V=V):
+    """The initial table of every test (computed once per k and V, never changed)."""
+    if (k, V) not in _TABLES:
         rng = np.random.default_rng(1000 + k)
-        _TABLES[k] = (rng.uniform(-0.05, 0.05, V).astype(np.float32),
-                      rng.uniform(-0.05, 0.05, (V, k)).astype(np.float32))
-    return _TABLES[k]
+        if V <= 1 << 20:
+            _TABLES[k, V] = (rng.uniform(-0.05, 0.05, V).astype(np.float32),
+                             rng.uniform(-0.05, 0.05, (V, k)).astype(np.float32))
+        else:  # a large table: drawn in fp32, and not kept
+            return (rng.random(V, np.float32) * np.float32(0.1) - np.float32(0.05),
+                    rng.random((V, k), np.float32) * np.float32(0.1) - np.float32(0.05))
+    return _TABLES[k, V]
 
 
 class Triple:
     """model + table + optimiser with known initial parameters."""
 
-    def __init__(self, kind, F, k, opt_kind, fc=FC, bias=0.01, **hyper):
+    def __init__(self, kind, F, k, opt_kind, fc=FC, bias=0.01, V=V, **hyper):
         self.ctx = rmx.default_context()
-        self.kind, self.F, self.k = kind, F, k
-        self.model = make_model(kind, F, k, fc)
+        self.kind, self.F, self.k, self.V = kind, F, k, V
+        self.model = make_model(kind, F, k, fc, V)
         self.mats0 = self.model.initMats(0x3A75) if kind != "lr" else np.zeros(0, np.float32)
         if kind != "lr":
             self.model.setMats(self.mats0)
         self.model.setBias(bias)
         self.bias0 = np.float32(bias)
-        self.w0, self.e0 = table_values(k)
+        self.w0, self.e0 = table_values(k, V)
         self.table = rmx.EmbeddingTable(self.ctx, V, k)
         self.table.upload(self.w0, self.e0)
         self.opt = rmx.Optimizer(self.model, self.table, opt_kind, **hyper)
@@ -72,6 +77,7 @@ class Triple:
         pw, pe = ctypes.c_void_p(), ctypes.c_void_p()
         _lib.check(_lib.lib.rmx_table_device_ptrs(self.table.handle, ctypes.byref(pw), ctypes.byref(pe)))
         self.ctx.sync()
+        V = self.V
         w = rmx.DeviceArray(self.ctx, V, np.float32, pw, self.table).numpy()
         e = rmx.DeviceArray(self.ctx, V * self.k, np.float32, pe, self.table).numpy().reshape(V, self.k)
         return w, e
@@ -80,7 +86,7 @@ class Triple:
         p = [ctypes.c_void_p() for _ in range(4)]
         _lib.check(_lib.lib.rmx_optim_state_ptrs(self.opt.handle, slot, *[ctypes.byref(x) for x in p]))
         self.ctx.sync()
-        sizes = (V, V * self.k, len(self.mats0), 1)
+        sizes = (self.V, self.V * self.k, len(self.mats0), 1)
         return [rmx.DeviceArray(self.ctx, n, np.float32, x, self.opt).numpy() if x.value else None
                 for x, n in zip(p, sizes)]
 
@@ -103,18 +109,18 @@ class Triple:
         self.model.close()
 
 
-def triple(kind, F, k, opt_kind, fc=FC, **hyper):
-    t = Triple(kind, F, k, opt_kind, fc, **hyper)
+def triple(kind, F, k, opt_kind, fc=FC, V=V, **hyper):
+    t = Triple(kind, F, k, opt_kind, fc, V=V, **hyper)
     t._hp = R.hyper(opt_kind, **hyper)
     return t
 
 
-def batch(seed, B, F, k, n_mats, hot=False):
+def batch(seed, B, F, k, n_mats, hot=False, V=V):
     """ids [B * F] in [0, V) and synthetic per-nonzero gradients."""
     rng = np.random.default_rng(seed)
     ids = rng.integers(0, V, (B, F)).astype(np.int32)
     if hot:
-        ids[:, 0] = 1234  # one id B times: with B > 512 its list takes the chunk path
+        ids[:, 0] = min(1234, V - 1)  # one id B times: with B > 512 its list takes the chunk path
     nnz = B * F
     return dict(ids=ids.reshape(-1), g_bias=rng.normal(0, 1, 1).astype(np.float32),
                 g_w=rng.normal(0, 1, nnz).astype(np.float32), g_emb=rng.normal(0, 1, (nnz, k)).astype(np.float32),
@@ -155,7 +161,12 @@ def assert_params_bitwise(t, ref, what=""):
 
 # ------------------------------------------------------------------ apply, bitwise ----
 BITWISE = [("deepfm", 37, 39, 16, False), ("deepfm", 512, 39, 16, False), ("deepfm", 600, 3, 16, True),
-           ("deepfm", 37, 6, 4, False), ("lr", 37, 39, 16, False), ("dnn", 37, 39, 16, False)]
+           ("deepfm", 37, 6, 4, False), ("lr", 37, 39, 16, False), ("dnn", 37, 39, 16, False),
+           # tab_update_kernel<false> / tab_long_kernel<false> walk a row in 16-column chunks: one partial chunk
+           # (k = 1, 5), two with a partial last one (k = 20), two full ones (k = 32); a hot id (> 512 occurrences)
+           # takes tab_long_kernel<false> over two chunks (k = 20) and over a partial one (k = 5)
+           ("deepfm", 37, 6, 1, False), ("deepfm", 37, 6, 5, False), ("deepfm", 37, 6, 20, False),
+           ("deepfm", 37, 6, 32, False), ("deepfm", 600, 6, 20, True), ("deepfm", 600, 6, 5, True)]
 
 
 @pytest.mark.parametrize("kind,B,F,k,hot", BITWISE, ids=["%s-B%d-F%d-k%d" % c[:4] for c in BITWISE])
@@ -205,6 +216,50 @@ def test_apply_skips_ids_outside_the_table_and_null_groups():
         t.close()
 
 
+RADIX_V = [(255, 1), (256, 2), (65535, 2), (65536, 3), (16_777_300, 4)]
+
+
+@pytest.mark.parametrize("Vt,passes", RADIX_V, ids=["V%d" % v for v, _ in RADIX_V])
+def test_apply_sgd_bitwise_radix_passes(Vt, passes):
+    """The radix sort of the ids makes 1, 2, 3 or 4 passes (after an odd count of ping-pong passes the sorted keys
+    lie in the other buffer): SGD at eta = 1.0 on a table of Vt rows, a few ids outside [0, Vt) -- Vt itself, the
+    largest key, among them -- bit for bit against the reference."""
+    assert R.radix_passes(Vt)[1] == passes
+    B, F, k = 37, 6, 4
+    t = triple("deepfm", F, k, "sgd", V=Vt, eta=1.0)
+    try:
+        b = batch(3 * passes + 1, B, F, k, len(t.mats0), V=Vt)
+        b["ids"][[0, 5, 17, 100, 3]] = [-1, Vt, Vt + 12345, np.iinfo(np.int32).max, np.iinfo(np.int32).min]
+        b["ids"][[7, 8]] = [Vt - 1, 0]
+        ref = t.ref(np.float32)
+        ref_apply(ref, b)
+        dev_apply(t, b, B)
+        got = assert_params_bitwise(t, ref)
+        inside = b["ids"][(b["ids"] >= 0) & (b["ids"] < Vt)]
+        untouched = np.ones(Vt, bool)
+        untouched[inside] = False
+        assert same_bits(got["w"][untouched], t.w0[untouched])
+        assert np.all(got["w"][~untouched] != t.w0[~untouched])
+    finally:
+        t.close()
+
+
+def test_apply_sgd_bitwise_scan_scale():
+    """nnz = 8,200 x 39 = 319,800 > 262,144: the histogram scan of a sort pass has more than one block of block
+    sums to add."""
+    B, F, k = 8200, 39, 16
+    assert B * F > 262144
+    t = triple("deepfm", F, k, "sgd", eta=1.0)
+    try:
+        b = batch(4242, B, F, k, len(t.mats0))
+        ref = t.ref(np.float32)
+        ref_apply(ref, b)
+        dev_apply(t, b, B)
+        assert_params_bitwise(t, ref)
+    finally:
+        t.close()
+
+
 # ------------------------------------------------------------------ apply, numeric ----
 @pytest.mark.parametrize("opt_kind,hyper", [("momentum", dict(eta=0.05)), ("adagrad", dict(eta=0.05)),
                                             ("adam", dict(eta=0.05))], ids=["momentum", "adagrad", "adam"])
@@ -242,6 +297,50 @@ def test_apply_numeric_three_steps(opt_kind, hyper):
             prev_got = got
         assert t.opt.steps == 3
         print("%s worst relative error %.3g" % (opt_kind, worst))
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("opt_kind", ["momentum", "adagrad", "adam"])
+@pytest.mark.parametrize("kind", ["deepfm", "dnn"])
+def test_apply_numeric_three_steps_k20(kind, opt_kind):
+    """The same three steps at k = 20 -- two 16-column chunks per row, the second partial, in the stateful
+    optimisers' update loops -- on DeepFM and on DNN (no first-order group: w and its states stay as they are)."""
+    B, F, k = 64, 6, 20
+    t = triple(kind, F, k, opt_kind, eta=0.05)
+    try:
+        ref = t.ref(np.float64)
+        names = [n for n in ("w", "emb", "mats", "bias") if getattr(ref, n) is not None]
+        assert ("w" in names) == (kind != "dnn") and "emb" in names
+        prev_got = dict(w=t.w0, emb=t.e0, mats=t.mats0, bias=t.bias0)
+        worst = 0.0
+        for step in range(3):
+            b = batch(700 + step, B, F, k, len(t.mats0))
+            prev_ref = {n: np.array(getattr(ref, n), np.float64) for n in names}
+            ref_apply(ref, b)
+            dev_apply(t, b, B)
+            got = t.params()
+            for name in names:
+                d_got = np.asarray(got[name], np.float64) - np.asarray(prev_got[name], np.float64)
+                d_ref = np.asarray(getattr(ref, name), np.float64) - prev_ref[name]
+                err = np.abs(d_got.reshape(-1) - d_ref.reshape(-1)).max() / np.abs(d_ref).max()
+                worst = max(worst, err)
+                assert err <= NUM_BAR, (name, step, err)
+            if kind == "dnn":
+                assert same_bits(got["w"], t.w0)
+            for slot in range(R.NSLOTS[opt_kind]):
+                sw, se, sm, sb = t.read_state(slot)
+                for name, g, r in (("w", sw, ref.s_w), ("emb", se, ref.s_emb), ("mats", sm, ref.s_mats),
+                                   ("bias", sb, ref.s_bias)):
+                    if name not in names:
+                        continue
+                    r = np.asarray(r[slot], np.float64).reshape(-1)
+                    err = np.abs(np.asarray(g, np.float64) - r).max() / np.abs(r).max()
+                    worst = max(worst, err)
+                    assert err <= NUM_BAR, (name, slot, step, err)
+            prev_got = got
+        assert t.opt.steps == 3
+        print("%s %s k=20 worst relative error %.3g" % (kind, opt_kind, worst))
     finally:
         t.close()
 
@@ -333,6 +432,58 @@ def test_repack_consistency_after_train_steps(kind, lines):
             t.close()
     finally:
         rmx.set_tuning("table_lines", None)
+
+
+def _sweep_rows():
+    import shape_cases as sc
+    return [c.name for c in sc.CASES if not sc.backward_refused(c) and c.name != "lr_f1k16"]
+
+
+@pytest.mark.parametrize("name", _sweep_rows())
+def test_repack_consistency_sweep_rows(name):
+    """The same off the tuned shape (shape_cases.py; LR once, no row whose backward is refused): after two
+    train_step_ids at B = 37 the trained model's forward equals, bit for bit, that of a fresh model given getMats() /
+    getBias() -- at B = 37 and at B = 16,400, where the large-batch tiles read other packed forms."""
+    import shape_cases as sc
+    c = sc.BY_NAME[name]
+    ctx = rmx.default_context()
+    rng = np.random.default_rng(90)
+    Vs = sc.V
+    m = sc.rmx_model(name)
+    mats0, bias0 = m.getMats() if c.kind != "lr" else None, m.getBias()
+    table = rmx.EmbeddingTable(ctx, Vs, c.k)
+    table.upload(rng.uniform(-0.05, 0.05, Vs).astype(np.float32),
+                 rng.uniform(-0.05, 0.05, (Vs, c.k)).astype(np.float32))
+    opt = rmx.Optimizer(m, table, "adam", eta=0.01)
+    fresh = None
+    try:
+        for step in range(2):
+            ids = rmx.DeviceArray.from_numpy(ctx, rng.integers(0, Vs, 37 * c.F).astype(np.int32))
+            tg = rmx.DeviceArray.from_numpy(ctx, (rng.random(37) > 0.6).astype(np.float32))
+            loss = m.train_step_ids(table, opt, 37, ids, tg)
+            assert np.isfinite(loss) and loss > 0
+        mats, bias = (m.getMats() if c.kind != "lr" else None), m.getBias()
+        assert bias != bias0 and (c.kind == "lr" or not same_bits(mats, mats0))
+        fresh = sc.rmx_model(name)
+        if c.kind != "lr":
+            fresh.setMats(mats)
+        fresh.setBias(bias)
+        for B in (37, 16400):
+            ids = rmx.DeviceArray.from_numpy(ctx, rng.integers(0, Vs, B * c.F).astype(np.int32))
+            outs = []
+            for mm in (m, fresh):
+                out = rmx.DeviceArray(ctx, B, np.float32)
+                mm.forward_ids(table, B, ids, out)
+                ctx.sync()
+                outs.append(out.numpy().copy())
+            assert np.isfinite(outs[0]).all()
+            assert same_bits(outs[0], outs[1]), (name, B, float(np.abs(outs[0] - outs[1]).max()))
+    finally:
+        if fresh is not None:
+            fresh.close()
+        opt.close()
+        table.close()
+        m.close()
 
 
 # ---------------------------------------------------------- step = backward + apply ----

@@ -110,6 +110,19 @@ def test_reference_sparse_semantics():
     assert ref.bias[0] != 0.5 and ref.t == 1
 
 
+def test_radix_passes_of_the_table_sizes_under_test():
+    """The id sort's key width and pass count (optim.hip id_bits, (bits + 7) / 8) at the table sizes of
+    test_optim.py: every V up to 5,003 of the other tests sorts in 2 passes; 255 is the last V of one pass, 65,536
+    the first of three, 2^24 the first of four (the bench's V = 1,000,000 makes three)."""
+    sizes = (255, 256, 65535, 65536, 16_777_300)
+    assert [R.radix_passes(V) for V in sizes] == [(8, 1), (9, 2), (16, 2), (17, 3), (25, 4)]
+    assert [R.radix_passes(V)[1] for V in (1, 2000, 5003, 1_000_000, (1 << 24) - 1, 1 << 24)] == [1, 2, 2, 3, 3, 4]
+    for V in (255, 256, 65535, 65536, 16_777_300):
+        bits, passes = R.radix_passes(V)
+        assert V < 1 << bits and V >= 1 << (bits - 1)  # V, the key of an outside id, fits; no spare bit
+        assert 8 * (passes - 1) < bits <= 8 * passes
+
+
 # ------------------------------------------------------------ create's checks (host) ----
 def _create(model_handle, table, kind, hyper, n=None):
     h = ctypes.c_void_p()
