@@ -161,8 +161,22 @@ int rmx_model_set_bias(rmx_model* m, float bias);
 /* RMX_DTYPE_BF16: Linear weights stored bf16 (rounded to nearest even when mats are loaded), the
  * towers on bf16 MFMA with fp32 accumulation, stored activations bf16 (BASELINE.json configs[4]).
  * Biases, the output Linear and DCN cross vectors stay fp32.  Call before rmx_model_set_mats.
- * L-B needs a table of the same dtype; L-A rounds the caller's fp32 arrays.  Not for xDeepFM. */
+ * L-B needs a table of the same dtype; L-A rounds the caller's fp32 arrays.  Not for xDeepFM (its
+ * CIN alone takes bf16 operands: rmx_model_set_cin_precision). */
 int rmx_model_set_precision(rmx_model* m, int dtype);
+/* xDeepFM only.  RMX_DTYPE_BF16: the CIN layers run on bf16 MFMA with fp32 accumulation.  The table, the
+ * DNN tower, the first order, the pooled sums, the output Linear and every stored activation stay fp32
+ * (the model's precision stays RMX_DTYPE_F32: it still takes an fp32 table or shard).
+ * Two values are stored bf16, each rounded once to nearest even: the CIN weights C_l, element by element
+ * as given in mats, when the mats are loaded (rmx_model_get_mats still returns the caller's fp32 values);
+ * and the generated operand z[f * H_prev + h] = bf16(fl32(x0[f] * u_prev[h])).  Accumulation, CIN biases,
+ * ReLU, the maps u_l kept between layers, the sum-pool and the CIN slice of the output Linear are fp32.
+ * Call before rmx_model_set_mats (it drops the loaded parameters); setting the current value does nothing.
+ * RMX_E_INVALID for a NULL or host-only model, a model that is not an xDeepFM, or another dtype.
+ * Forward only: on a bf16-CIN model rmx_backward, rmx_backward_ids, rmx_backward_pulled, rmx_optim_create,
+ * rmx_optim_create_sharded, rmx_train_step_ids and rmx_train_step_sharded fail with RMX_E_INVALID. */
+int rmx_model_set_cin_precision(rmx_model* m, int dtype);
+int rmx_model_get_cin_precision(const rmx_model* m);   /* RMX_DTYPE_F32 (default) / RMX_DTYPE_BF16; <0 on NULL */
 
 /* ---------------------------------------------------------------- table ---- */
 /* HBM-resident first-order weights + embedding table (replaces the Angel PS rows

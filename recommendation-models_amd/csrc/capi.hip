@@ -254,6 +254,20 @@ extern "C" int rmx_model_set_precision(rmx_model* m, int dtype) {
   return model_set_precision(*m, dtype);
 }
 
+extern "C" int rmx_model_set_cin_precision(rmx_model* m, int dtype) {
+  CHECK_ARG(m, "rmx_model_set_cin_precision: model is NULL");
+  CHECK_ARG(m->ctx, "rmx_model_set_cin_precision: host-only model (created without a context)");
+  CHECK_ARG(m->type == RMX_MODEL_XDEEPFM, "rmx_model_set_cin_precision: model is not an xDeepFM (no CIN)");
+  CHECK_ARG(dtype == RMX_DTYPE_F32 || dtype == RMX_DTYPE_BF16,
+            "rmx_model_set_cin_precision: dtype must be F32 or BF16");
+  ModelUse use(*m, m->ctx->stream);
+  if (use.st) return use.st;
+  if (dtype == m->cin_precision) return RMX_OK;
+  return model_set_cin_precision(*m, dtype);
+}
+
+extern "C" int rmx_model_get_cin_precision(const rmx_model* m) { return m ? m->cin_precision : -1; }
+
 extern "C" int rmx_model_set_bias(rmx_model* m, float bias) {
   CHECK_ARG(m, "rmx_model_set_bias: model is NULL");
   std::lock_guard<std::mutex> lk(m->mu);
@@ -680,6 +694,7 @@ extern "C" int rmx_backward_ids(rmx_model* m, const rmx_table* t, int32_t B, con
                                 float* d_g_mats, float* d_loss, void* stream) {
   CHECK_ARG(m && t && B >= 0, "rmx_backward_ids: bad args");
   CHECK_ARG(m->ctx, "rmx_backward_ids: host-only model (created without a context)");
+  if (int st = cin_bf16_rejects("rmx_backward_ids", m)) return st;
   CHECK_ARG((d_ids && d_targets) || B == 0, "rmx_backward_ids: ids / targets is NULL");
   if (!m->params_ready && m->mats_len > 0) {
     set_error("rmx_backward_ids: call rmx_model_set_mats first");
@@ -754,6 +769,7 @@ int rmx::optim_new(const char* who_c, rmx_model* m, int kind, const double* hype
   CHECK_WHO(kind != RMX_OPTIM_ADAM || (o->a < 1.0 && o->b < 1.0), "Adam needs beta, gamma < 1");
   CHECK_WHO(m->ctx, "host-only model (created without a context)");
 #undef CHECK_WHO
+  if (int st = cin_bf16_rejects(who_c, m)) return st;
   o->m = m;
   o->upd_w = m->type != RMX_MODEL_DNN;
   o->upd_e = m->type != RMX_MODEL_LR;
@@ -856,6 +872,7 @@ extern "C" int rmx_train_step_ids(rmx_model* m, const rmx_table* t, rmx_optim* o
   CHECK_ARG(!o->sh, "rmx_train_step_ids: the optimiser holds a shard (rmx_train_step_sharded)");
   CHECK_ARG(o->m == m && o->t == t, "rmx_train_step_ids: the optimiser belongs to another model / table");
   CHECK_ARG(d_targets || B == 0, "rmx_train_step_ids: targets is NULL");
+  if (int cst = cin_bf16_rejects("rmx_train_step_ids", m)) return cst;
   int st = optim_ready("rmx_train_step_ids", o, B, d_ids);
   if (st) return st;
   RMX_HIP(hipSetDevice(m->ctx->device));
@@ -918,6 +935,7 @@ extern "C" int rmx_backward(rmx_model* m, int32_t B, int64_t nnz, const int64_t*
   (void)fields;
   CHECK_ARG(m, "rmx_backward: model is NULL");
   CHECK_ARG(m->ctx, "rmx_backward: host-only model (created without a context)");
+  if (int st = cin_bf16_rejects("rmx_backward", m)) return st;
   CHECK_ARG(B >= 0 && nnz >= 0, "rmx_backward: negative batch_size / nnz");
   if (!targets && B > 0) { set_error("key not found: targets"); return RMX_E_INVALID; }
   bool regular = false, sorted = false;

@@ -324,7 +324,11 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
   constexpr bool BF = PREC == kPrecBF16, S3 = PREC == kPrecS3;
   constexpr int KC = (BF || S3) ? 32 : 16;       // K elements per step
   constexpr int KCA = BF ? 32 : 16, KSA = KCA / 4;  // A elements per 64-B row / per 16-B slot
-  static_assert(!BF || AMODE != kCinOuter, "CIN has no bf16 configuration");
+  // bf16 CIN (k_cin_bf16.hip): the generated operand z = x0 * u is formed in fp32, rounded to bf16 (RNE) and
+  // multiplied with the one bf16 plane of C_l; u, bias, ReLU and the rowdot stay fp32.  Like kPrecS3 it takes
+  // a 32-wide K step as two 16-wide generated chunks (one u cache each, a paired last h-chunk).
+  constexpr bool CB = BF && AMODE == kCinOuter;
+  constexpr bool C32 = S3 || CB;
   static_assert(!S3 || T::BKC == 1, "kPrecS3 stages one K step at a time");
   constexpr int MT = T::MT, NTW = T::NTW, WN = T::WN, BKC = T::BKC;
   constexpr int BM = T::BM, BN = T::BN, NTHR = T::NTHR;
@@ -536,7 +540,7 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
 
   // kCinOuter: the row's u[h-chunk] for the current hc, reloaded when hc changes (kPrecS3: one
   // cache per half of the 32-wide step, whose two 16-wide chunks may sit in different h-chunks)
-  constexpr int NU = S3 ? 2 : 1;
+  constexpr int NU = C32 ? 2 : 1;
   float4 uf[NU][MT];
   int cur_hc[NU];
 #pragma unroll
@@ -580,7 +584,7 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
       // except a paired last h-chunk p.cin_pair_hc (its chunk j carries fields 2j, 2j + 1)
       const int hc = div_f(c16);
       const int j = c16 - hc * F;
-      const int pr = S3 && hc == p.cin_pair_hc ? 1 : 0;
+      const int pr = C32 && hc == p.cin_pair_hc ? 1 : 0;
       f = pr ? 2 * j + (g >> 1) : j;
       key = hc * 2 + pr;
     }
@@ -615,6 +619,23 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
   // static in LDS)
   float x0q[2][MT];
   int kq[2] = {0, 0};
+  // bf16 CIN: the A fragments of 32-wide K step c.  Each z = fl32(x0 * u) is rounded once to bf16 (RNE,
+  // v_cvt_pk_bf16_f32); bf16 position 4h + q of lane group g is K index 16h + 4g + q of the step, the order
+  // of the weight plane (pack_cin_bf16_kernel) and of the split path's fragments.
+  auto cin_a_bf16 = [&](int c, bf16x8* a) {
+    f32x4 a0[MT], a1[MT];
+    if (c == 0) {
+      cin_x0(0, x0q[0], kq[0]);
+      cin_x0(1, x0q[1], kq[1]);
+    }
+    cin_a_x(0, 2 * c, x0q[0], kq[0], a0);
+    cin_a_x(1, 2 * c + 1, x0q[1], kq[1], a1);
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const bf16x4 lo = __builtin_convertvector(a0[i], bf16x4), hi = __builtin_convertvector(a1[i], bf16x4);
+      a[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+  };
 
   // kPrecS3: one 32-wide K step c.  Lane group g holds, at bf16 position 4h + q of its fragment,
   // K index 16h + 4g + q of the step (fp32 chunk 2c + h, slot g) -- the order W3 is packed in.
@@ -720,9 +741,13 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
   // next stages' DMAs ride one per MFMA group (same structure as compute_step_s3, 1/6 the MFMAs)
   auto compute_step_bf16 = [&](const float* cur, int c, auto&& dma) {
     bf16x8 a[MT];
+    if constexpr (A_LDS) {
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
-      a[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(cur + arow[i] * 16 + swz_slot(arow[i], g) * 4));
+      for (int i = 0; i < MT; ++i)
+        a[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(cur + arow[i] * 16 + swz_slot(arow[i], g) * 4));
+    } else {
+      cin_a_bf16(c, a);
+    }
     const float* Bt = cur + AROWS * 16;
     auto ldb = [&](int t) -> f32x4 {
       const int row = (bt0 + t) * 16 + r16;
@@ -736,6 +761,11 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
     for (int t = 0; t < NTW; ++t) {
       if (t + PF < NTW) bq[(t + PF) % (PF + 1)] = ldb(t + PF);
       if (t < kIPW) dma(t);
+      if constexpr (!A_LDS)
+        if (t == 0) {
+          cin_x0(2 * c + 2, x0q[0], kq[0]);
+          cin_x0(2 * c + 3, x0q[1], kq[1]);
+        }
       __builtin_amdgcn_sched_barrier(0);
       const bf16x8 b = __builtin_bit_cast(bf16x8, bq[t % (PF + 1)]);
 #pragma unroll
@@ -763,6 +793,13 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
           a[i] = *reinterpret_cast<const f32x4*>(At + arow[i] * 16 + swz_slot(arow[i], g) * 4);
         if constexpr (WRING)
           if (wfuse) wsum(c);
+      } else if constexpr (CB) {
+        bf16x8 ab[MT];
+        cin_a_bf16(c, ab);
+        cin_x0(2 * c + 2, x0q[0], kq[0]);
+        cin_x0(2 * c + 3, x0q[1], kq[1]);
+#pragma unroll
+        for (int i = 0; i < MT; ++i) a[i] = __builtin_bit_cast(f32x4, ab[i]);
       } else {
         cin_a(0, c, a);
       }
@@ -1266,7 +1303,7 @@ __global__ __launch_bounds__(T::NTHR, T::OCC) void gemm_kernel(GemmArgs p) {
               for (int e = 0; e < 4; ++e) v[e] += gz * (sv[e] - xv[e]) / 16.0f;
             }
           }
-          if constexpr (BF)
+          if constexpr (BF && !CB)
             *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(dst) + o) = __builtin_convertvector(v, bf16x4);
           else if (p.nt_store)
             __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + o));

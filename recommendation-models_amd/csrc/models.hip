@@ -456,6 +456,45 @@ int model_set_precision(rmx_model& m, int dtype) {
   return RMX_OK;
 }
 
+// The fp32 CIN's device forms of one layer (model_build allocates the same set)
+static int alloc_cin_f32(const rmx_model& m, CinLayer& c) {
+  int st;
+  if ((st = c.W.alloc((size_t)c.Hp_pad * m.F * c.Npad, "model"))) return st;
+  if ((st = c.W3.alloc(split3_elems(c.Hp_pad / kChunk * m.F, c.Npad), "model"))) return st;
+  if ((st = c.Wm.alloc((size_t)c.ncm * c.Npad * 16, "model"))) return st;
+  if ((st = c.WT.alloc((size_t)c.KTpad * c.NTpad, "model"))) return st;
+  return c.WT3.alloc(split3_elems(c.KTpad / kChunk, c.NTpad), "model");
+}
+
+// Switch the CIN layers between the fp32 forms and the one bf16 weight plane (before set_mats).  A bf16-CIN
+// model reads none of W / W3 / Wm / WT / WT3 (its backward is rejected), so they are dropped; the chunk map,
+// the biases and the output slices stay.
+int model_set_cin_precision(rmx_model& m, int dtype) {
+  RMX_HIP(hipSetDevice(m.ctx->device));
+  RMX_HIP(hipStreamSynchronize(m.ctx->stream));
+  m.params_ready = false;
+  for (auto& c : m.cin_layers) {
+    c.W.reset();
+    c.W3.reset();
+    c.Wm.reset();
+    c.WT.reset();
+    c.WT3.reset();
+    c.W16.reset();
+    const int st = dtype == kBF16 ? c.W16.alloc((size_t)cin_bf16_elems(m.F, c.Hp, c.Npad), "model")
+                                  : alloc_cin_f32(m, c);
+    if (st) return st;  // (out of memory: params_ready is off, and model_repack refuses the missing forms)
+  }
+  m.cin_precision = dtype;
+  return RMX_OK;
+}
+
+int cin_bf16_rejects(const char* who, const rmx_model* m) {
+  if (!m || m->cin_precision != kBF16) return RMX_OK;
+  set_error(std::string(who) +
+            ": not defined for a bf16 CIN (forward only; rmx_model_set_cin_precision(RMX_DTYPE_F32) to train)");
+  return RMX_E_INVALID;
+}
+
 // Every packed form the forward and the backward read, rebuilt on stream s from mats_dev (layer planes,
 // split-3 planes, transposes, CIN maps, wo, the DCN vectors): the device half of model_load_mats, and what
 // the optimiser runs after it has updated mats_dev in place (optim.hip).  The values the model keeps on the
@@ -472,6 +511,16 @@ int model_repack(rmx_model& m, hipStream_t s) {
     if ((st = copy_slice(s, m.mats_dev + m.wo_off, last.N, last.Npad, m.wo))) return st;
   }
   for (auto& c : m.cin_layers) {
+    if (m.cin_precision == kBF16 ? !c.W16 : !(c.W && c.W3 && c.Wm && c.WT && c.WT3)) {
+      set_error("model: CIN weight buffers missing (an rmx_model_set_cin_precision call ran out of memory)");
+      return RMX_E_INVALID;
+    }
+    if (m.cin_precision == kBF16) {  // the one bf16 plane, rounded from mats_dev as given (k_cin_bf16.hip)
+      if ((st = launch_pack_cin_bf16(s, m.mats_dev, m.F, c))) return st;
+      if ((st = copy_slice(s, m.mats_dev + c.b_off, c.H, c.Npad, c.b))) return st;
+      if ((st = copy_slice(s, m.mats_dev + c.wo_off, c.H, c.Npad, c.wo))) return st;
+      continue;
+    }
     if ((st = launch_pack_cin(s, m.mats_dev, m.F, c))) return st;
     // knob "cin_map" (default 1): the split planes in the chunk-map order (layer 1 folded to h <= f,
     // paired fields on a half-live h-chunk); 0: the plain hc * F + f order of c.W
@@ -802,9 +851,12 @@ int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in) {
       StageTimer t(m, s, l == 0 ? "cin_layer1" : (l == 1 ? "cin_layer2" : "cin_layer3+"));
       const bool last = l + 1 == m.cin_layers.size();
       float* uout = last ? nullptr : m.ws.ubuf[l & 1];
-      if ((st = launch_cin_layer(s, m.cin_layers[l], l == 0, last, B, F, k, in.ids, (const float*)in.table, uprev, uout,
-                                 m.ws.rowdot)))
-        return st;
+      st = m.cin_precision == kBF16
+               ? launch_cin_layer_bf16(s, m.cin_layers[l], l == 0, last, B, F, k, in.ids, (const float*)in.table, uprev,
+                                       uout, m.ws.rowdot)
+               : launch_cin_layer(s, m.cin_layers[l], l == 0, last, B, F, k, in.ids, (const float*)in.table, uprev, uout,
+                                  m.ws.rowdot);
+      if (st) return st;
       uprev = uout;
     }
     oa.rowsum = m.ws.rowdot;

@@ -135,6 +135,9 @@ struct CinLayer {
   DevBuf<float> WT;
   DevBuf<bf16_t> WT3;
   int KTpad = 0, NTpad = 0;
+  // bf16 CIN (rmx_model_set_cin_precision, k_cin_bf16.hip): C_l rounded to bf16, [steps][Npad][32] in the
+  // unfolded K order; the model then holds no W / W3 / Wm / WT / WT3 for the layer
+  DevBuf<bf16_t> W16;
 };
 
 }  // namespace rmx
@@ -167,6 +170,7 @@ struct rmx_model {
   rmx::CrossScalars cross_scalars{};
   rmx::DevBuf<int32_t> pairs;               // PNN (row, col) pairs [P][2]
   int precision = 0;                        // kF32 / kBF16 (rmx_model_set_precision)
+  int cin_precision = 0;                    // kF32 / kBF16 (rmx_model_set_cin_precision; xDeepFM)
   bool params_ready = false;
   float beta = 0.f;
   bool beta_set = false;
@@ -315,6 +319,9 @@ int model_load_mats(rmx_model& m, const float* host_mats, bool sync);
 // the packed forms rebuilt from mats_dev on stream s (no host values: bo / cross_scalars stay as they are)
 int model_repack(rmx_model& m, hipStream_t s);
 int model_set_precision(rmx_model& m, int dtype);
+int model_set_cin_precision(rmx_model& m, int dtype);
+// backward and optimisers are not defined for a bf16 CIN: RMX_E_INVALID (message set) on such a model
+int cin_bf16_rejects(const char* who, const rmx_model* m);
 int model_forward(rmx_model& m, hipStream_t s, const FwdInputs& in);
 // models whose every table read takes a row stride (DeepFM / DNN at k = 16, LR): they can read
 // [emb | w | pad] line rows in place (FwdInputs::ld / wld)
@@ -415,6 +422,11 @@ std::vector<int> cin_chunk_map(int F, int Hp, bool tri);
 int launch_pack_cin_map(hipStream_t s, const float* mats, int F, CinLayer& L);
 int launch_pack_cin_t(hipStream_t s, const float* mats_dev, int F, CinLayer& c);
 int launch_cin_dz_s3(hipStream_t s, const CinLayer& c, int rows, const float* gpre, int ldg, float* dz, int ldz);
+int64_t cin_bf16_elems(int F, int Hp, int Npad);
+int launch_pack_cin_bf16(hipStream_t s, const float* mats, int F, CinLayer& L);
+int launch_cin_layer_bf16(hipStream_t s, const CinLayer& L, bool first, bool last, int B, int F, int k,
+                          const int32_t* ids, const float* table, const float* u_prev, float* u_out, float* rowdot,
+                          int ld = 0);
 int launch_cin_layer(hipStream_t s, const CinLayer& L, bool first, bool last, int B, int F, int k,
                      const int32_t* ids, const float* table, const float* u_prev, float* u_out,
                      float* rowdot, int ld = 0);

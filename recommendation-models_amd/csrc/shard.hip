@@ -2121,6 +2121,7 @@ extern "C" int rmx_backward_pulled(rmx_model* m, rmx_shard* sh, int32_t B, int s
     set_error("rmx_backward_pulled: bad args (slot must be 0 or 1)");
     return RMX_E_INVALID;
   }
+  if (int cst = cin_bf16_rejects("rmx_backward_pulled", m)) return cst;
   int st = pulled_model_checks("rmx_backward_pulled", m, sh);
   if (st) return st;
   RMX_HIP(hipSetDevice(m->ctx->device));
@@ -2183,6 +2184,7 @@ extern "C" int rmx_train_step_sharded(rmx_model* m, rmx_shard* sh, rmx_optim* o,
     set_error(std::string(who) + ": bad args");
     return RMX_E_INVALID;
   }
+  if (int cst = cin_bf16_rejects(who, m)) return cst;
   if (o->m != m || o->sh != sh) {
     set_error(std::string(who) + (o->sh ? ": the optimiser belongs to another model / shard"
                                         : ": the optimiser holds a table (rmx_train_step_ids)"));

@@ -1680,6 +1680,7 @@ int model_train(rmx_model& m, hipStream_t s, const FwdInputs& in, const TrainOut
     set_error("backward: fp32 models only (rmx_model_set_precision(RMX_DTYPE_F32))");
     return RMX_E_INVALID;
   }
+  if (int cst = cin_bf16_rejects("backward", &m)) return cst;
   if (t == RMX_MODEL_DCN && m.cross_depth > kMaxFusedCross) {
     set_error("backward: DCN crossDepth must be <= " + std::to_string(kMaxFusedCross));
     return RMX_E_INVALID;

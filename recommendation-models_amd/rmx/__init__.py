@@ -746,6 +746,16 @@ class RecModel:
         """DTYPE_BF16: bf16 weights / activations on bf16 MFMA with fp32 accumulation (before setMats)."""
         check(_lib.lib.rmx_model_set_precision(self._device(), int(dtype)))
 
+    def setCinPrecision(self, dtype):
+        """xDeepFM only.  DTYPE_BF16: the CIN layers on bf16 MFMA with fp32 accumulation -- the CIN weights and the
+        generated operand x0 * u rounded to bf16, everything else (table, tower, stored maps, pooling) fp32.
+        Before setMats; forward only (backward and optimisers then raise)."""
+        check(_lib.lib.rmx_model_set_cin_precision(self._device(), int(dtype)))
+
+    def getCinPrecision(self):
+        """DTYPE_F32 (default) or DTYPE_BF16 (rmx_model_get_cin_precision)."""
+        return int(_lib.lib.rmx_model_get_cin_precision(self._dev if self._dev else self._meta))
+
     def setBias(self, bias):
         check(_lib.lib.rmx_model_set_bias(self._device(), float(np.asarray(bias).reshape(-1)[0])))
 

@@ -73,6 +73,8 @@ SIGNATURES = [
     ("rmx_table_create_ex", c_int, [c_vp, c_i64, c_int, c_int, P(c_vp)]),
     ("rmx_table_dtype", c_int, [c_vp]),
     ("rmx_model_set_precision", c_int, [c_vp, c_int]),
+    ("rmx_model_set_cin_precision", c_int, [c_vp, c_int]),
+    ("rmx_model_get_cin_precision", c_int, [c_vp]),
     ("rmx_table_destroy", c_int, [c_vp]),
     ("rmx_table_upload", c_int, [c_vp, P(c_f32), P(c_f32), c_int]),
     ("rmx_table_fill_synthetic", c_int, [c_vp, c_u64]),
