@@ -410,27 +410,27 @@ __global__ __launch_bounds__(256) void pack_lines_kernel(int64_t V, const T* __r
                                                         T* __restrict__ line) {
   constexpr int E = 16 / sizeof(T);  // elements per 16-B piece
   constexpr int P = 32 / E;          // pieces per line row
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t i = t / P;
-  const int c = (int)(t - i * P);
-  if (i >= V) return;
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c < 16 / E) {
-    v = reinterpret_cast<const float4*>(emb + i * 16)[c];
-  } else if (c == 16 / E) {
-    T* e = reinterpret_cast<T*>(&v);
-    e[0] = w[i];
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < V * P; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / P;
+    const int c = (int)(t - i * P);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < 16 / E) {
+      v = reinterpret_cast<const float4*>(emb + i * 16)[c];
+    } else if (c == 16 / E) {
+      T* e = reinterpret_cast<T*>(&v);
+      e[0] = w[i];
+    }
+    reinterpret_cast<float4*>(line + i * 32)[c] = v;
   }
-  reinterpret_cast<float4*>(line + i * 32)[c] = v;
 }
 
 int launch_pack_lines(hipStream_t s, int64_t V, const void* emb, const void* w, void* line, int dt) {
   if (V <= 0) return RMX_OK;
   if (dt == kBF16)
-    hipLaunchKernelGGL(pack_lines_kernel<bf16_t>, dim3((unsigned)((V * 4 + 255) / 256)), dim3(256), 0, s, V,
+    hipLaunchKernelGGL(pack_lines_kernel<bf16_t>, dim3(elem_blocks(V * 4)), dim3(256), 0, s, V,
                        (const bf16_t*)emb, (const bf16_t*)w, (bf16_t*)line);
   else
-    hipLaunchKernelGGL(pack_lines_kernel<float>, dim3((unsigned)((V * 8 + 255) / 256)), dim3(256), 0, s, V,
+    hipLaunchKernelGGL(pack_lines_kernel<float>, dim3(elem_blocks(V * 8)), dim3(256), 0, s, V,
                        (const float*)emb, (const float*)w, (float*)line);
   RMX_HIP(hipGetLastError());
   return RMX_OK;
@@ -438,25 +438,25 @@ int launch_pack_lines(hipStream_t s, int64_t V, const void* emb, const void* w, 
 
 template <class T>
 __global__ void fill_table_kernel(uint64_t seed, int64_t V, int k, float scale, T* w, T* emb) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t tot = V * (k + 1);
-  if (i >= tot) return;
-  const int64_t id = i / (k + 1);
-  const int j = (int)(i - id * (k + 1));
-  const uint64_t h = splitmix64(seed ^ (uint64_t)i);  // i == id*(k+1) + j
-  const float v = (float)((int32_t)(h >> 40) - 8388608) * scale;
-  if (j < k) st1(emb + id * k + j, v);
-  else st1(w + id, v);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t id = i / (k + 1);
+    const int j = (int)(i - id * (k + 1));
+    const uint64_t h = splitmix64(seed ^ (uint64_t)i);  // i == id*(k+1) + j
+    const float v = (float)((int32_t)(h >> 40) - 8388608) * scale;
+    if (j < k) st1(emb + id * k + j, v);
+    else st1(w + id, v);
+  }
 }
 
 int launch_fill_table(hipStream_t s, uint64_t seed, int64_t V, int k, void* w, void* emb, int dt) {
   const int64_t tot = V * (k + 1);
   const float scale = 0.05f * (1.0f / 8388608.0f);
   if (dt == kBF16)
-    hipLaunchKernelGGL(fill_table_kernel<bf16_t>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, seed, V, k,
+    hipLaunchKernelGGL(fill_table_kernel<bf16_t>, dim3(elem_blocks(tot)), dim3(256), 0, s, seed, V, k,
                        scale, (bf16_t*)w, (bf16_t*)emb);
   else
-    hipLaunchKernelGGL(fill_table_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, seed, V, k,
+    hipLaunchKernelGGL(fill_table_kernel<float>, dim3(elem_blocks(tot)), dim3(256), 0, s, seed, V, k,
                        scale, (float*)w, (float*)emb);
   RMX_HIP(hipGetLastError());
   return RMX_OK;
@@ -492,25 +492,25 @@ int launch_gather(hipStream_t s, int64_t n, const int32_t* ids, const void* wtab
 }
 
 __global__ void convert_bf16_kernel(const float* __restrict__ src, int64_t n, bf16_t* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (bf16_t)src[i];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = (bf16_t)src[i];
 }
 
 __global__ void widen_bf16_kernel(const bf16_t* __restrict__ src, int64_t n, float* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (float)src[i];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = (float)src[i];
 }
 
 int launch_widen_bf16(hipStream_t s, const bf16_t* src, int64_t n, float* dst) {
   if (n <= 0) return RMX_OK;
-  hipLaunchKernelGGL(widen_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, n, dst);
+  hipLaunchKernelGGL(widen_bf16_kernel, dim3(elem_blocks(n)), dim3(256), 0, s, src, n, dst);
   RMX_HIP(hipGetLastError());
   return RMX_OK;
 }
 
 int launch_convert_bf16(hipStream_t s, const float* src, int64_t n, bf16_t* dst) {
   if (n <= 0) return RMX_OK;
-  hipLaunchKernelGGL(convert_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, n, dst);
+  hipLaunchKernelGGL(convert_bf16_kernel, dim3(elem_blocks(n)), dim3(256), 0, s, src, n, dst);
   RMX_HIP(hipGetLastError());
   return RMX_OK;
 }
@@ -582,21 +582,21 @@ int launch_pack_linear(hipStream_t s, const float* mats_dev, DenseLayer& L) {
 
 template <class T>
 __global__ void transpose_kmajor_kernel(const float* __restrict__ src, int64_t V, int k, T* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= V * k) return;
-  const int64_t id = i / k;
-  const int j = (int)(i - id * k);
-  st1(dst + i, src[(int64_t)j * V + id]);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V * k; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t id = i / k;
+    const int j = (int)(i - id * k);
+    st1(dst + i, src[(int64_t)j * V + id]);
+  }
 }
 
 int launch_transpose_kmajor(hipStream_t s, const float* src_kv, int64_t V, int k, void* dst_vk, int dt) {
   const int64_t tot = V * k;
   if (tot <= 0) return RMX_OK;
   if (dt == kBF16)
-    hipLaunchKernelGGL(transpose_kmajor_kernel<bf16_t>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, src_kv,
+    hipLaunchKernelGGL(transpose_kmajor_kernel<bf16_t>, dim3(elem_blocks(tot)), dim3(256), 0, s, src_kv,
                        V, k, (bf16_t*)dst_vk);
   else
-    hipLaunchKernelGGL(transpose_kmajor_kernel<float>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, src_kv,
+    hipLaunchKernelGGL(transpose_kmajor_kernel<float>, dim3(elem_blocks(tot)), dim3(256), 0, s, src_kv,
                        V, k, (float*)dst_vk);
   RMX_HIP(hipGetLastError());
   return RMX_OK;

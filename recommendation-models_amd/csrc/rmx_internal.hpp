@@ -54,6 +54,17 @@ inline int cu_count_or(int def) {
   return cu_count(&ncu) == hipSuccess ? ncu : def;
 }
 
+// Blocks of 256 threads for a kernel with one thread per element of a whole table.  A launch of 2^32 threads or
+// more was observed to return no error and to leave most elements unwritten (V (k + 1) = 4.46e9 elements of a
+// k = 32 table: the first 168.8M written, which is the count's low 32 bits; 32 V = 4.33e9 of a line partition
+// likewise), so such a kernel walks its elements in a grid-stride loop,
+//   for (i = blockIdx.x * 256 + threadIdx.x; i < tot; i += gridDim.x * 256),
+// over at most 2^30 threads; below that the loop makes one trip, as before.
+inline unsigned elem_blocks(int64_t tot) {
+  const int64_t b = (tot + 255) / 256;
+  return (unsigned)(b < (int64_t(1) << 22) ? b : (int64_t(1) << 22));
+}
+
 // The row strides of a k = 16 gather as shifts: table rows of ld elements (0 = 16) and first-order weights wld
 // apart (0 = 1), both powers of two, ld >= 16 (the kernels form id << shift).  false: not such strides.
 inline bool gather_shifts(int ld, int wld, int& gsh, int& wsh) {

@@ -531,18 +531,19 @@ __device__ __forceinline__ uint64_t splitmix64_d(uint64_t x) {
 // (oracle orc_gen_table / fill_table_kernel): bit-identical to the replicated table's rows
 __global__ void shard_fill_kernel(uint64_t seed, int64_t V, int64_t rows_per, int N, int part, int k, int rs,
                                   float scale, float* __restrict__ rowsbuf, OwnerPerm op) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows_per * rs) return;
-  const int64_t l = i / rs;
-  const int j = (int)(i - l * rs);
-  const int64_t pid = l * N + part;                              // position in p's image
-  const int64_t id = pid < V ? owner_perm(pid, op, true) : V;    // the global id stored there
-  float v = 0.f;
-  if (id < V && j <= k) {  // j == k: the first-order weight; j > k: padding
-    const uint64_t h = splitmix64_d(seed ^ (uint64_t)(id * (k + 1) + j));
-    v = (float)((int32_t)(h >> 40) - 8388608) * scale;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows_per * rs;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t l = i / rs;
+    const int j = (int)(i - l * rs);
+    const int64_t pid = l * N + part;                              // position in p's image
+    const int64_t id = pid < V ? owner_perm(pid, op, true) : V;    // the global id stored there
+    float v = 0.f;
+    if (id < V && j <= k) {  // j == k: the first-order weight; j > k: padding
+      const uint64_t h = splitmix64_d(seed ^ (uint64_t)(id * (k + 1) + j));
+      v = (float)((int32_t)(h >> 40) - 8388608) * scale;
+    }
+    rowsbuf[i] = v;
   }
-  rowsbuf[i] = v;
 }
 
 }  // namespace
@@ -966,7 +967,7 @@ int shard_fill_synthetic(rmx_shard& sh, uint64_t seed) {
   for (float* q : sh.part) RMX_HIP(hipMemsetAsync(q + tot, 0, sizeof(float) * sh.rs, s));  // the zero row
   for (size_t p = 0; p < sh.part.size(); ++p) {
     const int part = sh.loopback ? (int)p : sh.rank;
-    hipLaunchKernelGGL(shard_fill_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, seed, sh.V,
+    hipLaunchKernelGGL(shard_fill_kernel, dim3(elem_blocks(tot)), dim3(256), 0, s, seed, sh.V,
                        sh.rows_per, sh.N, part, sh.k, sh.rs, scale, sh.part[p], owner_perm_of(sh));
     RMX_HIP(hipGetLastError());
   }

@@ -122,9 +122,37 @@ def gen_table(seed, V, k, id0=0, nrows=None):
     return w, emb.reshape(nrows, k)
 
 
+_U64 = np.uint64
+
+
+def _splitmix64_np(x):
+    """orc_splitmix64 on a uint64 array (the products wrap mod 2^64, as in C)."""
+    x = x + _U64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> _U64(27))) * _U64(0x94D049BB133111EB)
+    return x ^ (x >> _U64(31))
+
+
+def _unif_np(h, a):
+    """rmx_oracle.c unif: the top 24 bits, one exact int -> float conversion and one rounding multiply."""
+    scale = np.float32(a) * (np.float32(1.0) / np.float32(8388608.0))
+    return ((h >> _U64(40)).astype(np.int64) - 8388608).astype(np.float32) * scale
+
+
 def gen_rows(seed, V, k, ids):
     """Gathered rows (w[n], E[n*k:(n+1)*k]) of the generated table for arbitrary ids, generating
-    only those rows (a V = 100M table need not exist on the host)."""
+    only those rows (a V = 100M table need not exist on the host).  orc_gen_table restated on numpy arrays:
+    the same bits (test_big_table_cpu.py holds it to gen_rows_loop)."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    with np.errstate(over="ignore"):
+        base = ids.astype(_U64) * _U64(k + 1)
+        cols = base[:, None] + np.arange(k + 1, dtype=_U64)[None, :]
+        v = _unif_np(_splitmix64_np(_U64(seed) ^ cols), 0.05)
+    return np.ascontiguousarray(v[:, k]), np.ascontiguousarray(v[:, :k]).ravel()
+
+
+def gen_rows_loop(seed, V, k, ids):
+    """gen_rows one orc_gen_table call per id: the check of the vectorised form."""
     ids = np.asarray(ids, np.int64)
     w = np.zeros(len(ids), np.float32)
     e = np.zeros((len(ids), k), np.float32)
